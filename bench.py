@@ -221,6 +221,41 @@ def cpu_baseline_window(scene, p0, p1, flags, seed, first, steps, max_seconds, t
         return {"error": str(e)}
 
 
+DUMP_BODY_ROWS = 1 << 20  # (x, y, angle, vx, vy, w, awake, type) per body: 32 MB
+DUMP_CONTACT_ROWS = 1 << 16  # a seeded sample of the contacts sorted by ids: 5 + 16 values per contact
+DUMP_SEED = 20240601
+
+
+def _sample_rows(n, cap):
+    """All row indices when n <= cap, else a fixed seeded sample of `cap` of them in ascending order."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, w):
+    """--dump-outputs: what a caller of the timed Step() path holds after the last timed step, as .npy files (float32 /
+    float64, < 64 MB in all) for comparing two builds output for output:
+      bodies.npy             float32 [n, 8]  the body-state read-back: x, y, angle, vx, vy, w, awake, type (all bodies up to
+                                             DUMP_BODY_ROWS, else a seeded sample; body_rows.npy says which)
+      counts.npy             float64 [2]     body count, contact count
+      contact_ids.npy        float64 [k, 5]  body A, fixture A | child << 16, body B, fixture B | child << 16, flags (touching 1,
+                                             enabled 2) of a seeded sample of the contacts sorted by ids (all when <= DUMP_CONTACT_ROWS)
+      contact_manifolds.npy  float32 [k, 16] their manifolds: type, point count, local normal, local point, then per point local
+                                             point, normal / tangent impulse, id key (its bits)"""
+    os.makedirs(out_dir, exist_ok=True)
+    bodies = w.bodies()
+    rows = _sample_rows(bodies.shape[0], DUMP_BODY_ROWS)
+    np.save(os.path.join(out_dir, "bodies.npy"), bodies[rows])
+    if rows.size < bodies.shape[0]:
+        np.save(os.path.join(out_dir, "body_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([w.body_count, w.contact_count], np.float64))
+    ids, flags, man = w.contacts()
+    rows = _sample_rows(ids.shape[0], DUMP_CONTACT_ROWS)
+    np.save(os.path.join(out_dir, "contact_ids.npy"), np.concatenate([ids[rows], flags[rows, None]], axis=1).astype(np.float64))
+    np.save(os.path.join(out_dir, "contact_manifolds.npy"), man[rows])
+
+
 def gpu_window(amd, scene, p0, p1, flags, seed, first, steps):
     """The same scene on the GPU in the window [first, first + steps): what the reference's same-window figure stands beside."""
     w = amd.world(scene, p0, p1, seed=seed, flags=flags)
@@ -319,6 +354,8 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the multi-island roofline sample (500 k bodies in 100 k piles)")
     ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configs (Pyramid 141, 1 M field, 50 k pyramid)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of each CPU baseline (the headline's: twice that)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (body states, a seeded sample of the contacts) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -448,6 +485,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w)  # (the state the last timed step left, before anything else steps the world)
     if roof is None:
         roof = solver_roofline_pass()
     ctr = b2hip.Counters()

@@ -198,8 +198,21 @@ def _configure(L, optional_ok=False):
     return L
 
 
+def use_torch_hip_runtime():
+    """Make torch's HIP runtime the one libb2hip.so binds to. torch ships its own libamdhip64 / libhsa-runtime64 and asks for
+    them by another name, so a process that loads libb2hip.so first ends up with two HIP runtimes, and whichever of them opens
+    the device second finds none (hipGetDeviceCount: no ROCm-capable device). With torch imported first, libb2hip.so's
+    libamdhip64.so.7 resolves to torch's copy (same soname): one runtime. Call it before loading any library that links
+    libb2hip.so."""
+    try:
+        import torch  # noqa: F401
+    except ImportError:  # (no torch in the process: the system runtime is the only one)
+        pass
+
+
 def load(path, optional_ok=False):
     """Any library that exports the b2hip C ABI (the product, or the tests' oracle shim)."""
+    use_torch_hip_runtime()
     return _configure(C.CDLL(path), optional_ok)
 
 

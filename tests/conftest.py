@@ -8,6 +8,11 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(ROOT, "box2d-mt_amd", "python"))
 
+import b2hip  # noqa: E402
+
+# before any test loads a library that links libb2hip.so (some load it directly): one HIP runtime in the process
+b2hip.use_torch_hip_runtime()
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
