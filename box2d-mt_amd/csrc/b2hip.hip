@@ -26,11 +26,7 @@
 #include "../../include/b2hip.h"
 #include "b2d_kernels_toi_chains.h"
 #include "b2d_kernels_toi_domains.h"
-// (The three earlier resident large-island solvers of rounds 1 - 2 - grid barrier per colour, polled body rows, pushed
-// mailboxes - lived on as a test build until round 3 and were removed in round 4: k_solve_blocks / k_blocks_sweep are
-// cross-checked against the launch-per-colour kernels, tests/test_gpu_parity.py. What is left of them compiles out.)
 #include "b2d_handover.h"
-#define B2HIP_HAVE_VALIDATION_SOLVERS 0
 #include "b2d_kernels_solve_blocks.h"
 #include "b2d_kernels_sweep_end.h"
 #include "b2d_kernels_edit.h"

@@ -111,7 +111,7 @@ int b2hip_shard_connect(b2hip_world* w, const void* id128, int rank, int count)
 	ncclComm_t comm = nullptr;
 	RCCL_TRY(g_rccl.commInitRank(&comm, count, id, rank));
 	w->shardComm = comm;
-	w->shardLoopback = getenv("B2HIP_SHARD_LOOPBACK") != nullptr && atoi(getenv("B2HIP_SHARD_LOOPBACK")) != 0;
+	w->shardLoopback = envOn("B2HIP_SHARD_LOOPBACK");
 	w->dw.shardRank = rank;
 	w->dw.shardCount = count;
 	return B2HIP_OK;
@@ -149,8 +149,7 @@ static int spAllGather(b2hip_world* w, size_t words)
 {
 	const int ranks = w->dw.shardCount;
 	w->spBytesStep += 4 * words * (size_t)(ranks - 1);
-	static const bool trace = getenv("B2HIP_SHARD_TRACE") && atoi(getenv("B2HIP_SHARD_TRACE"));
-	if (trace && w->dw.shardRank == 0) fprintf(stderr, "[b2hip] step %lld: all-gather of %zu words per rank (caps: rows %d proxies %d pairs %d toi %d / %d / %d)\n",
+	if (w->shardTrace && w->dw.shardRank == 0) fprintf(stderr, "[b2hip] step %lld: all-gather of %zu words per rank (caps: rows %d proxies %d pairs %d toi %d / %d / %d)\n",
 		(long long)w->stepEpoch, words, w->spRowCap, w->spProxyCap, w->spPairCap, w->spToiBodyCap, w->spToiProxyCap, w->spTailCap);
 	if (w->spTapeFrom != nullptr)
 	{
@@ -675,7 +674,7 @@ int b2hip_shard_spatial(b2hip_world* w, int rank, int count, const uint8_t* owne
 		for (size_t k = 0; k < xs.size(); ++k) w->spOwners[(size_t)xs[k].second] = spStripOf(w, xs[k].first);
 	}
 	w->spatial = true;
-	w->spFullRows = getenv("B2HIP_SHARD_FULL_ROWS") != nullptr && atoi(getenv("B2HIP_SHARD_FULL_ROWS")) != 0;
+	w->spFullRows = envOn("B2HIP_SHARD_FULL_ROWS");
 	w->spOwnersDirty = true;
 	w->dw.shardRank = rank;
 	w->dw.shardCount = count;

@@ -589,7 +589,7 @@ static int stepEndImpl(b2hip_world* w)
 	}
 	if (w->toiChains && w->h_dstate->c.toiUnsafe != 0)
 	{
-		if (getenv("B2HIP_TOI_WHY")) fprintf(stderr, "b2hip: TOI fallback to the serial loop, unsafe bits 0x%x (1 partner, 2 woke, 4 new pair, 8 capacity, 16 moved proxies), %d pending, %d components\n", w->h_dstate->c.toiUnsafe, w->h_dstate->c.nToiList, w->h_dstate->c.nToiDomains);
+		if (w->toiWhy) fprintf(stderr, "b2hip: TOI fallback to the serial loop, unsafe bits 0x%x (1 partner, 2 woke, 4 new pair, 8 capacity, 16 moved proxies), %d pending, %d components\n", w->h_dstate->c.toiUnsafe, w->h_dstate->c.nToiList, w->h_dstate->c.nToiDomains);
 		// (a capacity cut - possibly more candidate contacts in one event than the narrow component loops have lanes: the wide form next time)
 		if (w->h_dstate->c.toiUnsafe & 8) w->toiDomWide = 64;
 		rc = toiSerial(w);
@@ -710,7 +710,7 @@ static int stepEndImpl(b2hip_world* w)
 	if ((c.overflow & 0x2040) == 0x2040) return setError(B2HIP_ERR_CAPACITY, "a block of the large-island partition holds more rows or home bodies than its workgroup takes (the census the host partitions by did not see them)");
 	if (c.overflow & 64)
 	{
-		if (getenv("B2HIP_HANDOVER_WHY")) handoverPostMortem(w);
+		if (w->handoverWhy) handoverPostMortem(w);
 		return setError(B2HIP_ERR_HIP, "a wait inside a resident large-island solver timed out (a workgroup was not resident, or a hand-over never came)");
 	}
 	if (c.overflow & SCAN_ABORT_BIT) return setError(B2HIP_ERR_HIP, "a single-pass scan gave up waiting for a predecessor tile (k_scan_chain look-back)");
@@ -800,7 +800,7 @@ static int stepEndImpl(b2hip_world* w)
 			w->ktBytes = (double)w->last.nLContacts * (w->sp.velIters * 220.0 + w->last.posItersLarge * 136.0 + 488.0) + (double)w->last.nLBodies * 240.0;
 			w->ktLaunches = w->familyLaunches;
 		}
-		else if (w->ktKind == 3 || w->ktKind == 4) w->ktBytes = (double)w->last.nLContacts * (w->sp.velIters * 220.0 + w->last.posItersLarge * 136.0 + 488.0) + (double)w->last.nLBodies * 240.0;
+		else if (w->ktKind == 4) w->ktBytes = (double)w->last.nLContacts * (w->sp.velIters * 220.0 + w->last.posItersLarge * 136.0 + 488.0) + (double)w->last.nLBodies * 240.0;
 		else w->ktBytes = (double)w->last.nSContacts * (w->sp.velIters * 220.0 + w->sp.posIters * 136.0 + 488.0) + (double)w->last.nSBodies * 240.0;
 	}
 	return 0;

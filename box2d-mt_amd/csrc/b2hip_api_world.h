@@ -47,8 +47,6 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 		delete w;
 		return setError(B2HIP_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
 	}
-	w->debugSync = getenv("B2HIP_DEBUG") != nullptr;
-	w->forceLarge = getenv("B2HIP_FORCE_LARGE") ? atoi(getenv("B2HIP_FORCE_LARGE")) : 0;
 	w->nextNode = 0;
 	w->leafCount = 0;
 	w->upBodies = w->upFixtures = w->upShapes = w->upJoints = 0;
@@ -79,91 +77,37 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 	w->dw.invCellSize = 1.0f;
 	w->toiRan = false;
 	w->toiEventValid = false;
-	w->debugTrace = getenv("B2HIP_TRACE") != nullptr;
-	w->kernelTimingLaunches = getenv("B2HIP_SOLVER_LAUNCHES") != nullptr; // force the launch-per-colour solver
-	w->solverBarriers = getenv("B2HIP_SOLVER_BARRIERS") != nullptr;       // persistent kernel with a grid barrier per colour instead of body-level dataflow
-	w->persistSteps = 0;
 	w->colorSmallPending = false;
 	w->hubSteps = 0;
-	w->useGraphs = getenv("B2HIP_GRAPHS") != nullptr; // opt-in: measured no gain on MI355X (the step is not host-bound), see DESIGN.md
-	w->graphCaptures = 0;
-	w->persistMaxWG = 0;
-	w->nCU = 256;
+	readSwitches(w);
 	{
+		// how many workgroups of the solvers whose workgroups wait for one another are resident together on this device
 		hipDeviceProp_t prop;
 		int devId = 0;
 		if (hipGetDevice(&devId) == hipSuccess && hipGetDeviceProperties(&prop, devId) == hipSuccess)
 		{
-			w->nCU = prop.multiProcessorCount;
-#if B2HIP_HAVE_VALIDATION_SOLVERS
-			int perCU = 0, perCU2 = 0;
-			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_solve_dataflow, PERSIST_LANES, 0) == hipSuccess &&
-				hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU2, k_solve_mailbox<true>, PERSIST_LANES, 0) == hipSuccess)
+			int perCU = 0, perCU2 = 0, perCU3 = 0;
+			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_solve_blocks<256>, 256, 0) == hipSuccess &&
+				hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU2, k_solve_blocks<512>, 512, 0) == hipSuccess &&
+				hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU3, k_solve_blocks<BLOCK_LANES>, BLOCK_LANES, 0) == hipSuccess &&
+				perCU > 0 && perCU2 > 0 && perCU3 > 0)
 			{
-				perCU = std::min(perCU, perCU2);
-				// the occupancy query can be one block per CU high (sgpr_count 81-112, MI355X_MICROARCH.md): keep a margin
-				w->persistMaxWG = std::max(0, std::min(perCU - 1, 4)) * prop.multiProcessorCount;
+				// one block per CU is all this sizing relies on (the occupancy query can be one too high, MI355X_MICROARCH.md)
+				w->blocksMaxWG = prop.multiProcessorCount - 8;
+				int s0 = 0, s1 = 0, s2 = 0;
+				if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&s0, k_blocks_sweep<256>, 256, 0) == hipSuccess &&
+					hipOccupancyMaxActiveBlocksPerMultiprocessor(&s1, k_blocks_sweep<512>, 512, 0) == hipSuccess &&
+					hipOccupancyMaxActiveBlocksPerMultiprocessor(&s2, k_blocks_sweep<BLOCK_LANES>, BLOCK_LANES, 0) == hipSuccess)
+				{
+					// (the blocks of a launch wait for one another: all of them must be resident together)
+					w->sweepMaxWG[0] = std::max(1, s0 - 1) * w->blocksMaxWG;
+					w->sweepMaxWG[1] = std::max(1, s1 - 1) * w->blocksMaxWG;
+					w->sweepMaxWG[2] = std::max(1, s2 - 1) * w->blocksMaxWG;
+				}
 			}
-#else
-			w->persistMaxWG = 1 << 24; // (a limit of the cross-check solvers; k_solve_blocks has its own: blocksMaxWG)
-#endif
-		}
-	}
-	w->dfLanesForced = 0;
-	w->noSideStream = getenv("B2HIP_NO_SIDE_STREAM") != nullptr;
-	w->profileDetail = !(getenv("B2HIP_PROFILE_DETAIL") && atoi(getenv("B2HIP_PROFILE_DETAIL")) == 0);
-	if (const char* e = getenv("B2HIP_SOLID_ROUNDS")) { const int v = atoi(e); w->solidRoundsEnv = (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0; }
-	w->collideSplitEnv = getenv("B2HIP_COLLIDE_SPLIT") ? atoi(getenv("B2HIP_COLLIDE_SPLIT")) : -1;
-	w->collideUniOff = getenv("B2HIP_COLLIDE_UNI") && atoi(getenv("B2HIP_COLLIDE_UNI")) == 0;
-	w->collideSortEnv = getenv("B2HIP_COLLIDE_SORT") ? atoi(getenv("B2HIP_COLLIDE_SORT")) : -1;
-	w->collideStage = getenv("B2HIP_COLLIDE_STAGE") ? atoi(getenv("B2HIP_COLLIDE_STAGE")) : -1;
-	w->dfEpoch = 0;
-	// single-XCD attempt of k_solve_mailbox: opt-in. Measured on the 10k-body pyramid it LOSES (launch 500 us against 368):
-	// 334 waves polling on 32 CUs load the consumer CUs' memory queues, which is where a hand-off is priced; L2 locality
-	// buys only 0.1-0.3 us of it (MI355X_MICROARCH.md, handoff-1to1)
-	w->solverLocal = getenv("B2HIP_SOLVER_SINGLE_XCD") != nullptr;
-	w->solverRows = getenv("B2HIP_SOLVER_ROWS") != nullptr; // polled body rows (k_solve_dataflow) instead of pushed mailboxes
-	w->solverMailbox = getenv("B2HIP_SOLVER_MAILBOX") != nullptr; // pushed hand-offs for every constraint (k_solve_mailbox) instead of k_solve_blocks
-	w->noSweepBlocks = getenv("B2HIP_NO_SWEEP_BLOCKS") != nullptr;
-	w->tracePartition = getenv("B2HIP_TRACE_PARTITION") != nullptr;
-	if (const char* e = getenv("B2HIP_GRID_HALF")) { w->gridForced = true; w->gridHalf = atoi(e) != 0; w->dw.gridHalf = w->gridHalf ? 1 : 0; }
-	w->dw.noChainCreate = getenv("B2HIP_TOI_NO_CHAIN_CREATE") != nullptr ? 1 : 0;
-	w->dw.noOwnIdBlocks = getenv("B2HIP_NO_OWN_ID_BLOCKS") != nullptr ? 1 : getenv("B2HIP_OWN_ID_BLOCKS_ALL") != nullptr ? -1 : 0;
-	w->traceLaunches = getenv("B2HIP_TRACE_LAUNCHES") != nullptr;
-	w->noBlocks = getenv("B2HIP_NO_BLOCKS") != nullptr;           // no block partition at all (colours as before it existed)
-	w->blockLanes = 0; // chosen per partition (see phaseSolve); B2HIP_BLOCK_LANES = 256 | 512 | 1024 forces one size
-	if (const char* e = getenv("B2HIP_BLOCK_LANES")) w->blockLanes = atoi(e) == 512 ? 512 : (atoi(e) == 256 ? 256 : (atoi(e) == 1024 ? 1024 : 0));
-	{
-		int perCU = 0, perCU2 = 0, perCU3 = 0;
-		hipDeviceProp_t prop;
-		int devId = 0;
-		if (hipGetDevice(&devId) == hipSuccess && hipGetDeviceProperties(&prop, devId) == hipSuccess &&
-			hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_solve_blocks<256>, 256, 0) == hipSuccess &&
-			hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU2, k_solve_blocks<512>, 512, 0) == hipSuccess &&
-			hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU3, k_solve_blocks<BLOCK_LANES>, BLOCK_LANES, 0) == hipSuccess &&
-			perCU > 0 && perCU2 > 0 && perCU3 > 0)
-		{
-			// one block per CU is all this sizing relies on (the occupancy query can be one too high, MI355X_MICROARCH.md)
-			w->blocksMaxWG = prop.multiProcessorCount - 8;
-			int s0 = 0, s1 = 0, s2 = 0;
-			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&s0, k_blocks_sweep<256>, 256, 0) == hipSuccess &&
-				hipOccupancyMaxActiveBlocksPerMultiprocessor(&s1, k_blocks_sweep<512>, 512, 0) == hipSuccess &&
-				hipOccupancyMaxActiveBlocksPerMultiprocessor(&s2, k_blocks_sweep<BLOCK_LANES>, BLOCK_LANES, 0) == hipSuccess)
-			{
-				// (the blocks of a launch wait for one another: all of them must be resident together)
-				w->sweepMaxWG[0] = std::max(1, s0 - 1) * w->blocksMaxWG;
-				w->sweepMaxWG[1] = std::max(1, s1 - 1) * w->blocksMaxWG;
-				w->sweepMaxWG[2] = std::max(1, s2 - 1) * w->blocksMaxWG;
-			}
-		}
-	}
-	{
-		// the workgroups of k_large_rest / k_rest_hub wait for one another's rows: all of a launch must be resident together
-		// (the grid was sized from the colour census alone)
-		int devId = 0, r1 = 0, r2 = 0, f1 = 0, f2 = 0;
-		hipDeviceProp_t prop;
-		if (hipGetDevice(&devId) == hipSuccess && hipGetDeviceProperties(&prop, devId) == hipSuccess)
-		{
+			// the workgroups of k_large_rest / k_rest_hub wait for one another's rows: all of a launch must be resident together
+			// (the grid was sized from the colour census alone)
+			int r1 = 0, r2 = 0, f1 = 0, f2 = 0;
 			const int cus = std::max(1, prop.multiProcessorCount - 8);
 			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r1, k_large_rest<1>, 256, 0) == hipSuccess &&
 				hipOccupancyMaxActiveBlocksPerMultiprocessor(&r2, k_large_rest<2>, 256, 0) == hipSuccess && r1 > 0 && r2 > 0)
@@ -173,16 +117,8 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 				w->restHubMaxWG = std::min(f1, f2) * cus;
 		}
 	}
-	w->dfSleep = 1;
-	if (const char* e = getenv("B2HIP_DF_LANES")) w->dfLanesForced = std::max(64, std::min(256, atoi(e) / 64 * 64));
-	if (const char* e = getenv("B2HIP_DF_SLEEP")) w->dfSleep = atoi(e);
+	w->dfEpoch = 0;
 	w->toiChains = false;
-	w->toiSerialOnly = getenv("B2HIP_TOI_SERIAL") != nullptr;
-	w->toiSyncOnly = getenv("B2HIP_TOI_SYNC") != nullptr;
-	w->toiDomWideOnly = getenv("B2HIP_TOI_DOM_WIDE") != nullptr;
-	w->noToiSpecDomains = getenv("B2HIP_TOI_NO_SPEC_DOMAINS") != nullptr;
-	w->debugAssumeFreshGrid = getenv("B2HIP_DEBUG_ASSUME_FRESH_GRID") != nullptr;
-	w->toiNoDomains = getenv("B2HIP_TOI_NO_DOMAINS") != nullptr; // bullets / kinematic partners through the serial loop only // decide chains / serial loop from a read-back after k_toi_first (the older flow)
 	w->toiFallbacks = 0;
 	for (int i = 0; i < 13; ++i) w->ev[i] = nullptr;
 	w->h_dstate = nullptr;
@@ -214,7 +150,6 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 		return setError(B2HIP_ERR_HIP, "hipHostMalloc (coherent) failed");
 	}
 	memset(w->h_pub2, 0, sizeof(DState));
-	w->recoverOn = !(getenv("B2HIP_NO_RECOVER") && atoi(getenv("B2HIP_NO_RECOVER")));
 	if (hipHostMalloc((void**)&w->h_solverWord, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
 		hipHostGetDevicePointer((void**)&w->d_solverWord, w->h_solverWord, 0) != hipSuccess)
 	{
@@ -222,10 +157,6 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 		return setError(B2HIP_ERR_HIP, "hipHostMalloc (coherent) failed");
 	}
 	memset(w->h_solverWord, 0, 64);
-	w->noCensusPoll = getenv("B2HIP_NO_CENSUS_POLL") && atoi(getenv("B2HIP_NO_CENSUS_POLL"));
-	w->noStatePoll = getenv("B2HIP_NO_STATE_POLL") && atoi(getenv("B2HIP_NO_STATE_POLL"));
-	w->lazyReadback = getenv("B2HIP_LAZY_READBACK") && atoi(getenv("B2HIP_LAZY_READBACK"));
-	if (getenv("B2HIP_EARLY_ROWS_MIN")) w->earlyRowsMin = atoi(getenv("B2HIP_EARLY_ROWS_MIN"));
 	int rc = ensureCapacity(w, 0);
 	if (rc == 0 && hipStreamSynchronize(w->stream) != hipSuccess) rc = setError(B2HIP_ERR_HIP, "stream sync failed");
 	if (rc)
@@ -285,7 +216,7 @@ void b2hip_world_destroy(b2hip_world* w)
 	w->b_slot.release(); w->b_island.release(); w->chunkFirst.release();
 	w->li_bodies.release(); w->li_contacts.release(); w->li_roots.release(); w->li_color.release(); w->colorCount.release();
 	w->colorStart.release(); w->colorCursor.release(); w->li_sorted.release(); w->bodyClaim.release(); w->rootPen.release();
-	w->bodyActive.release(); w->bodyRest.release(); w->b_posv.release(); w->dfRank.release(); w->dfInbox.release(); w->evKey.release(); w->evInfo.release(); w->uncolList.release(); w->compactList.release(); w->gridBar.release(); w->hubRowOf.release(); w->hubList.release(); w->hubDelta.release(); w->hubMeta.release(); w->hubFirst.release(); w->solveSnapBody.release(); w->solveSnapImp.release(); w->solveSnapCFlags.release(); w->solveSnapJoints.release(); w->solveSnapGears.release();
+	w->bodyActive.release(); w->bodyRest.release(); w->b_posv.release(); w->evKey.release(); w->evInfo.release(); w->uncolList.release(); w->compactList.release(); w->gridBar.release(); w->hubRowOf.release(); w->hubList.release(); w->hubDelta.release(); w->hubMeta.release(); w->hubFirst.release(); w->solveSnapBody.release(); w->solveSnapImp.release(); w->solveSnapCFlags.release(); w->solveSnapJoints.release(); w->solveSnapGears.release();
 	w->b_proxyHead.release(); w->p_next.release(); w->toiList.release(); w->toiPos2c.release(); w->toiDestroyList.release(); w->toiNewList.release();
 	w->b_toiGroup.release(); w->toiGroups.release(); w->toiGroupCount.release(); w->toiGroupList.release(); w->toiMoved.release(); w->toiNew.release(); w->toiParent.release(); w->toiDomOf.release(); w->toiDomRoot.release(); w->toiDomCount.release(); w->toiDomBase.release(); w->toiDomFill.release(); w->toiDomFailed.release(); w->toiDomEvents.release(); w->toiDomList.release(); w->toiHull.release(); w->snapBody.release(); w->snapFat.release();
 	w->c_mgr[0].release(); w->c_mgr[1].release(); w->dbgPreVel.release(); w->dbgVel.release(); w->dbgLi.release();
@@ -309,14 +240,6 @@ void b2hip_world_destroy(b2hip_world* w)
 	for (int i = 0; i < 13; ++i)
 		if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
 	for (size_t i = 0; i < w->ktEvents.size(); ++i) (void)hipEventDestroy(w->ktEvents[i]);
-	{
-		GraphSeg* segs[3] = { &w->segCollide, &w->segIslands, &w->segPairs };
-		for (int i = 0; i < 3; ++i)
-		{
-			if (segs[i]->exec) (void)hipGraphExecDestroy(segs[i]->exec);
-			if (segs[i]->graph) (void)hipGraphDestroy(segs[i]->graph);
-		}
-	}
 	if (w->stream) (void)hipStreamDestroy(w->stream);
 	if (w->stream2) (void)hipStreamDestroy(w->stream2);
 	if (w->evFork) (void)hipEventDestroy(w->evFork);

@@ -145,9 +145,10 @@ static int runSortAndCreate(b2hip_world* w, bool largePath, long long knownPairs
 
 static int findNewContacts(b2hip_world* w, bool sync);
 static int findNewContactsOnce(b2hip_world* w, bool sync);
+// The pair update at the end of the step.
 static int findNewContactsGraph(b2hip_world* w)
 {
-	// (a user contact filter is asked on the host in the middle of the update: synchronous, no graph)
+	// (a user contact filter is asked on the host in the middle of the update: synchronous)
 	if (hasFilter(w) || w->spatial) return findNewContacts(w, true);
 	// A scene that creates more pairs per step than the optimistic counting path ranks (the settled 50 086-box pyramid and the
 	// 100 000-box Tumbler: ~25 000 and ~150 000 new fat-AABB pairs per step) would find that out at the end of the step, sort
@@ -157,8 +158,7 @@ static int findNewContactsGraph(b2hip_world* w)
 	// themselves - was built and measured in round 5, same box, same states: Tumbler 3.49 against 3.50 ms, Pyramid 316 1.37
 	// against 1.39, and the 1 M field 2.6 against 2.2: its updates alternate between 3 000 and 150 000 pairs, every second guess
 	// was too small and the update ran twice. The gaps a kernel trace shows behind this read-back are the profiler's.)
-	if (w->pairsLargeSticky > 0) return findNewContacts(w, true);
-	return runSegment(w, w->segPairs, 3, [w]() -> int { return findNewContacts(w, false); });
+	return findNewContacts(w, w->pairsLargeSticky > 0);
 }
 
 // The pair finder met more candidate pairs than the buffer holds (a dense start: every proxy is "moved" and overlaps dozens
@@ -246,35 +246,32 @@ static int phaseCollide(b2hip_world* w)
 	// TOI candidates is a launch of its own and the evaluation runs four waves per SIMD; below, the launch costs more than the
 	// occupancy gives)
 	const bool split = w->collideSplitEnv < 0 ? w->last.nContacts >= 262144 : w->collideSplitEnv != 0;
-	return runSegment(w, w->segCollide, 1 + (w->dw.preSolveOn ? 32 : 0) + (split ? 64 : 0), [w, split]() -> int
+	DW& d = w->dw;
+	if (int rk = ktBracket(w, 2, 5)) return rk;
+	// (shape records staged through LDS where the world holds many distinct ones: b2d_kernels_collide.h)
+	// Measured (tools/gpu_collide_variants.py, profiles/r04_collide_variants.txt): on the 1 M-body field (a record per body,
+	// circles / boxes / n-gons mixed) staging + sorting a tile by shape-pair class 133 -> 124 us; on the 100 000-box Tumbler
+	// (one record, one class) the sort costs 2 % - so both follow the number of distinct records unless the environment says otherwise.
+	const bool many = w->shapes.size() > 4096;
+	const bool stage = w->collideStage < 0 ? many : w->collideStage != 0;
+	// (round 6, measured and left out: sorting also by "the old manifold had points" - the pairs that will run the clipping - to
+	// give the one touching contact in six of a dense pile waves of its own: Tumbler 316 3.275 -> 3.338 ms, 1 M field 2.10 -> 2.14)
+	const int sort = w->collideSortEnv < 0 ? (many ? 1 : 0) : (w->collideSortEnv != 0 ? 1 : 0);
+	// (bit 2: the records of a workgroup's first contact staged in LDS, two staged 4-gons evaluated with unrolled loops -
+	// b2d_kernels_collide.h; Tumbler 316: 2.95 -> 2.88 ms. B2HIP_COLLIDE_UNI=0: off, the comparison form of the tests)
+	const int uni = w->collideUniOff ? 0 : 4;
+	if (stage) LAUNCH(w, (k_collide<1, true>), gridFor(d.capContacts), 256, d, sort);
+	else if (split)
 	{
-		DW& d = w->dw;
-		if (int rk = ktBracket(w, 2, 5)) return rk;
-		// (shape records staged through LDS where the world holds many distinct ones: b2d_kernels_collide.h)
-		// Measured (tools/gpu_collide_variants.py, profiles/r04_collide_variants.txt): on the 1 M-body field (a record per body,
-		// circles / boxes / n-gons mixed) staging + sorting a tile by shape-pair class 133 -> 124 us; on the 100 000-box Tumbler
-		// (one record, one class) the sort costs 2 % - so both follow the number of distinct records unless the environment says otherwise.
-		const bool many = w->shapes.size() > 4096;
-		const bool stage = w->collideStage < 0 ? many : w->collideStage != 0;
-		// (round 6, measured and left out: sorting also by "the old manifold had points" - the pairs that will run the clipping - to
-		// give the one touching contact in six of a dense pile waves of its own: Tumbler 316 3.275 -> 3.338 ms, 1 M field 2.10 -> 2.14)
-		const int sort = w->collideSortEnv < 0 ? (many ? 1 : 0) : (w->collideSortEnv != 0 ? 1 : 0);
-		// (bit 2: the records of a workgroup's first contact staged in LDS, two staged 4-gons evaluated with unrolled loops -
-		// b2d_kernels_collide.h; Tumbler 316: 2.95 -> 2.88 ms. B2HIP_COLLIDE_UNI=0: off, the comparison form of the tests)
-		const int uni = w->collideUniOff ? 0 : 4;
-		if (stage) LAUNCH(w, (k_collide<1, true>), gridFor(d.capContacts), 256, d, sort);
-		else if (split)
-		{
-			LAUNCH(w, (k_collide<0, false>), gridFor(d.capContacts), 256, d, sort | uni);
-			LAUNCH(w, k_toi_order_destroy, 1, 256, d);
-		}
-		else LAUNCH(w, (k_collide<0, true>), gridFor(d.capContacts), 256, d, sort | uni);
-		if (int rk = ktBracket(w, 2, 5)) return rk;
-		deviceExclusiveScan<int>(w->stream, d.keepFlag, d.keepScan, d.scanTmp, w->scanCtx, &d.st->c.nContacts, d.capContacts);
-		if (d.preSolveOn) LAUNCH(w, k_presolve_gather, gridFor(d.capContacts), 256, d);
-		LAUNCH(w, k_compact_contacts, gridFor(d.capContacts), 256, d); // (its last workgroup switches the buffers)
-		return 0;
-	});
+		LAUNCH(w, (k_collide<0, false>), gridFor(d.capContacts), 256, d, sort | uni);
+		LAUNCH(w, k_toi_order_destroy, 1, 256, d);
+	}
+	else LAUNCH(w, (k_collide<0, true>), gridFor(d.capContacts), 256, d, sort | uni);
+	if (int rk = ktBracket(w, 2, 5)) return rk;
+	deviceExclusiveScan<int>(w->stream, d.keepFlag, d.keepScan, d.scanTmp, w->scanCtx, &d.st->c.nContacts, d.capContacts);
+	if (d.preSolveOn) LAUNCH(w, k_presolve_gather, gridFor(d.capContacts), 256, d);
+	LAUNCH(w, k_compact_contacts, gridFor(d.capContacts), 256, d); // (its last workgroup switches the buffers)
+	return 0;
 }
 
 int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out);
@@ -312,118 +309,138 @@ static int partitionLargeIslands(b2hip_world* w, int targetDeg)
 	LAUNCH(w, k_part_assign, gridFor(d.nBodies), 256, d, vin, d.pairRank);
 	LAUNCH(w, k_color_recheck_begin, gridFor(d.nBodies), 256, d);
 	LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
-			LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
+	LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
 	LAUNCH(w, k_block_census, 1, 1024, d, (DState*)nullptr);
 	return 0;
 }
 
-// b2World::Solve (b2World.cpp:1166-1431): island build, census read-back, then the solver tier of each island.
-static int phaseSolve(b2hip_world* w)
+// ---- b2World::Solve (b2World.cpp:1166-1431): island build, census read-back, then the solver tier of each island --------
+// phaseSolve is the driver; the stages below hand one SolveStep on. What a stage decides for the rest of the step is written
+// there: a recovery, for one, rewrites the colours and the solver choice before the large islands are solved a second time.
+struct SolveStep
 {
-	w->trace.clear();
-	w->blocksThisStep = false;
+	Counters c;                       // the island census as the host last read it (stages refresh its colour census)
+	bool poll = false;                // the census is published to pinned memory and polled (B2HIP_NO_CENSUS_POLL=1: copy + synchronise)
+	bool largeHint = false;           // the world has had large islands lately: the island build took the colour census too
+	bool exactLarge = false;          // B2HIP_FORCE_LARGE=2: every island through the large-island solver in the reference's order
+	bool colorSmallQueued = false;    // k_color_small went out behind the census and has work to do
+	bool colorAheadPublished = false; // ... in its no-partition mode: it publishes the state behind it
+	bool plainIslands = false;        // no joints, no hub body
+	bool blockShape = false;          // the large islands are to have a block partition
+	bool hasJoints = false, hasHubs = false; // (hasHubs: anything for k_large_hub)
+	bool sideStream = false;          // the small-island chain runs on the side stream ...
+	bool smallDeferred = false;       // ... and is still to be launched (behind the large-island solver's first launches)
+	int nLIslands = 0, nLBodies = 0, nLContacts = 0, nColors = 0; // what the large-island solver runs over
+	bool useBlocks = false;           // k_solve_blocks
+	bool useSweep = false;            // k_blocks_sweep (else a launch per colour)
+	bool colorsOnDevice = false;      // k_solve_blocks reads the colour count on the device
+	bool censusVoid = false;          // colours were handed out afresh: the colour census of this step is history
+	bool colorSpill = false;          // some constraint found no free colour this step: it sits in the hub group and is swept in order
+	bool waitsBetweenWorkgroups = false; // the solve used a kernel whose workgroups wait for one another
+};
+
+static const int RECOLOR_SLACK = 2; // colour afresh when the colours in use exceed the last fresh colouring's by more than this
+
+// The island build, up to the publication of its census (b2dPublishCensus): by k_block_census, by k_island_edges when that is
+// the last kernel, else by a launch of its own.
+static int buildIslands(b2hip_world* w, const SolveStep& s)
+{
 	DW& d = w->dw;
-	d.serialOrphans = w->serialOrphansNext;
-	const StepParams& sp = w->sp;
-	if (w->kernelTiming <= 1)
-	{
-		// (the event pairs of the solver kernels belong to this phase; those of k_collide / k_sync_fixtures / k_find_pairs_small -
-		// timing modes 2 to 4 - are taken in other phases of the step and cleared by b2hip_step_begin)
-		w->ktUsed = 0;
-		w->ktKind = 0;
-	}
-	const int forceLarge = w->forceLarge;
-	// (the step parameters are kernel arguments of k_island_classify - it steps the free bodies - so a captured segment is
-	// only replayed for the same ones)
-	uint64_t spHash = 1469598103934665603ull;
-	for (size_t k = 0; k < sizeof(StepParams); ++k) spHash = (spHash ^ ((const unsigned char*)&sp)[k]) * 1099511628211ull;
-	const bool largeHint = w->largeHintSteps > 0;
-	// the island build ends with the publication of its census (b2dPublishCensus): by k_block_census, by k_island_edges when
-	// that is the last kernel, else by a launch of its own. B2HIP_NO_CENSUS_POLL=1: copy + stream synchronisation instead.
-	const bool poll = !w->noCensusPoll;
 	const bool adopt = w->adoptPasses;
-	const int pubBy = !poll ? 0 : (largeHint ? 1 : ((d.nJoints == 0 && !adopt) ? 2 : 3));
+	const int pubBy = !s.poll ? 0 : (s.largeHint ? 1 : ((d.nJoints == 0 && !adopt) ? 2 : 3));
 	// (the passes over the contacts gather the solid ones of a tile of `solidRounds` x 256 contacts in LDS, b2d_kernels_island.h:
 	// tiles as large as leave a thousand workgroups with one each - a lane per contact below 512 000 contacts)
 	int solidRounds = 1;
 	while (solidRounds < SOLID_TILE_ROUNDS_MAX && (long long)w->last.nContacts >= 2ll * solidRounds * 256 * 1024) solidRounds *= 2;
 	if (w->solidRoundsEnv > 0) solidRounds = w->solidRoundsEnv;
-	const int solidIdx = solidRounds >= 8 ? 3 : (solidRounds >= 4 ? 2 : (solidRounds >= 2 ? 1 : 0));
-	int rc = runSegment(w, w->segIslands, (2 + 16ull * (uint64_t)forceLarge + (largeHint ? 8ull : 0ull) + 64ull * (uint64_t)pubBy + (adopt ? 512ull : 0ull) + 1024ull * (uint64_t)solidIdx) ^ (spHash << 12), [w, forceLarge, sp, largeHint, pubBy, adopt, solidRounds]() -> int
+	const int gSolid = gridFor((size_t)(d.capContacts + solidRounds - 1) / solidRounds);
+	LAUNCH(w, k_island_init, gridFor(d.nBodies), 256, d);
+	LAUNCH(w, k_island_union, gSolid, 256, d, solidRounds);
+	LAUNCH(w, k_island_flatten, gridFor(d.nBodies), 256, d);
+	LAUNCH(w, k_island_count, gSolid, 256, d, solidRounds);
+	LAUNCH(w, k_island_classify, gridFor(d.nBodies), 256, d, w->forceLarge, w->sp);
+	if (d.shardCount > 1 && !d.spatial) LAUNCH(w, k_shard_big, 1, 1024, d); // the big islands of a sharded world, dealt over the ranks
+	deviceExclusiveScan<int4>(w->stream, d.rootScanIn, d.rootScanOut, w->scanTmp4.p, w->scanCtx, w->consts.p, d.nBodies);
+	if (hipError_t le = hipGetLastError()) return setError(B2HIP_ERR_HIP, std::string("k_scan<int4> launch: ") + hipGetErrorString(le));
+	deviceExclusiveScan<int>(w->stream, d.deg, d.adjStart, d.scanTmp, w->scanCtx, w->consts.p, d.nBodies);
+	if (d.nJoints > 0) deviceExclusiveScan<int>(w->stream, d.rootJoints, d.rootJointStart, d.scanTmp, w->scanCtx, w->consts.p, d.nBodies);
+	LAUNCH(w, k_island_assign, gridFor(d.nBodies), 256, d);
+	LAUNCH(w, k_island_edges, gSolid, 256, d, pubBy == 2 ? w->d_pub : (DState*)nullptr, solidRounds);
+	// (a growing pile: hand home blocks on to newcomers up to four contacts away instead of partitioning again)
+	if (adopt)
+		for (int stage = 0; stage < 3; ++stage) LAUNCH(w, k_block_adopt, gridFor(d.capContacts), 256, d, stage);
+	if (d.nJoints > 0) LAUNCH(w, k_joints_fill, gridFor(d.nJoints), 256, d);
+	// (colour bookkeeping and block census only matter to large islands: skipped while the world has had none lately)
+	if (s.largeHint)
 	{
-		DW& d = w->dw;
-		LAUNCH(w, k_island_init, gridFor(d.nBodies), 256, d);
-		LAUNCH(w, k_island_union, gridFor((size_t)(d.capContacts + solidRounds - 1) / solidRounds), 256, d, solidRounds);
-		LAUNCH(w, k_island_flatten, gridFor(d.nBodies), 256, d);
-		LAUNCH(w, k_island_count, gridFor((size_t)(d.capContacts + solidRounds - 1) / solidRounds), 256, d, solidRounds);
-		LAUNCH(w, k_island_classify, gridFor(d.nBodies), 256, d, forceLarge, sp);
-		if (d.shardCount > 1 && !d.spatial) LAUNCH(w, k_shard_big, 1, 1024, d); // the big islands of a sharded world, dealt over the ranks
-		{
-			int blocks = (d.nBodies + SCAN_TILE - 1) / SCAN_TILE;
-			if (blocks < 1) blocks = 1;
-			deviceExclusiveScan<int4>(w->stream, d.rootScanIn, d.rootScanOut, w->scanTmp4.p, w->scanCtx, w->consts.p, d.nBodies);
-			if (hipError_t le = hipGetLastError()) return setError(B2HIP_ERR_HIP, std::string("k_scan<int4> launch: ") + hipGetErrorString(le));
-		}
-		deviceExclusiveScan<int>(w->stream, d.deg, d.adjStart, d.scanTmp, w->scanCtx, w->consts.p, d.nBodies);
-		if (d.nJoints > 0)
-		{
-			deviceExclusiveScan<int>(w->stream, d.rootJoints, d.rootJointStart, d.scanTmp, w->scanCtx, w->consts.p, d.nBodies);
-		}
-		LAUNCH(w, k_island_assign, gridFor(d.nBodies), 256, d);
-		LAUNCH(w, k_island_edges, gridFor((size_t)(d.capContacts + solidRounds - 1) / solidRounds), 256, d, pubBy == 2 ? w->d_pub : (DState*)nullptr, solidRounds);
-		// (a growing pile: hand home blocks on to newcomers up to four contacts away instead of partitioning again)
-		if (adopt)
-			for (int stage = 0; stage < 3; ++stage) LAUNCH(w, k_block_adopt, gridFor(d.capContacts), 256, d, stage);
-		if (d.nJoints > 0) LAUNCH(w, k_joints_fill, gridFor(d.nJoints), 256, d);
-		// (colour bookkeeping and block census only matter to large islands: skipped while the world has had none lately)
-		if (largeHint)
-		{
-			LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
-			LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
-			LAUNCH(w, k_block_census, 1, 1024, d, pubBy == 1 ? w->d_pub : (DState*)nullptr);
-		}
-		if (pubBy == 3) LAUNCH(w, k_publish_census, 1, 256, d, w->d_pub);
-		return 0;
-	});
-	if (rc) return rc;
+		LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
+		LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
+		LAUNCH(w, k_block_census, 1, 1024, d, pubBy == 1 ? w->d_pub : (DState*)nullptr);
+	}
+	if (pubBy == 3) LAUNCH(w, k_publish_census, 1, 256, d, w->d_pub);
+	return 0;
+}
 
-	// the host needs the island census to size the solver launches
-	bool colorSmallQueued = false;
-	bool colorAheadPublished = false; // the queued k_color_small ran in its no-partition mode and publishes the state behind it
-	int aheadMinRows = 0;
-	if (poll)
+// The host needs the island census to size the solver launches.
+static int awaitIslandCensus(b2hip_world* w, SolveStep& s)
+{
+	DW& d = w->dw;
+	int rc = 0;
+	if (s.poll)
 	{
 		w->pubSeq = (w->pubSeq + 1) & 0x3fffffff; // (the device counts its publications the same way: DState::pubCount)
 		// what the host would launch next in the usual case (a few new contacts on a settled pile to colour, a colour class to
 		// compact) goes behind the census at once and runs while the host is busy with it; the kernel looks at the same
 		// counters and returns if the case is another one
 		// (round 6: ... and where no partition can be made this step - the large islands are beyond what the block solvers take,
-		// the host's own hysteresis below - the queued launch runs too and PUBLISHES what it leaves: the launch-per-colour path
-		// polls that instead of a copy + synchronise)
-		aheadMinRows = (forceLarge != 2 && !w->colorAheadOff) ? (w->noBlocks ? 1 : (w->blocksTooBig ? 650 * std::max(w->blocksMaxWG, w->sweepMaxWG[2]) : 0)) : 0;
-		if (largeHint && forceLarge != 2) { LAUNCH(w, k_color_small, 1, 1024, d, 1, aheadMinRows, w->d_pub2, (w->pubSeq2 + 1) & 0x3fffffff); colorSmallQueued = true; }
+		// the host's own hysteresis in largeIslandPolicy - the queued launch runs too and PUBLISHES what it leaves: the
+		// launch-per-colour path polls that instead of a copy + synchronise)
+		const int aheadMinRows = s.exactLarge ? 0 : (w->noBlocks ? 1 : (w->blocksTooBig ? 650 * std::max(w->blocksMaxWG, w->sweepMaxWG[2]) : 0));
+		if (s.largeHint && !s.exactLarge) { LAUNCH(w, k_color_small, 1, 1024, d, 1, aheadMinRows, w->d_pub2, (w->pubSeq2 + 1) & 0x3fffffff); s.colorSmallQueued = true; }
 		rc = awaitCensus(w);
 		if (rc == 0)
 		{
 			const bool settled = b2dPartitionSettled(w->h_dstate->c);
-			colorAheadPublished = colorSmallQueued && b2dColorAheadNoPartition(w->h_dstate->c, aheadMinRows);
-			if (colorAheadPublished) w->pubSeq2 = (w->pubSeq2 + 1) & 0x3fffffff; // (its publication is on its way, with this number)
-			if (!settled && !colorAheadPublished) colorSmallQueued = false; // (it saw the same and returned)
+			s.colorAheadPublished = s.colorSmallQueued && b2dColorAheadNoPartition(w->h_dstate->c, aheadMinRows);
+			if (s.colorAheadPublished) w->pubSeq2 = (w->pubSeq2 + 1) & 0x3fffffff; // (its publication is on its way, with this number)
+			if (!settled && !s.colorAheadPublished) s.colorSmallQueued = false; // (it saw the same and returned)
 		}
 	}
 	else rc = readState(w);
 	if (rc) return rc;
-	Counters c = w->h_dstate->c;
+	s.c = w->h_dstate->c;
+	return 0;
+}
+
+// The colour census again, under one class (after a new partition, or without one), and the census read back.
+static int recheckColors(b2hip_world* w, SolveStep& s)
+{
+	DW& d = w->dw;
+	LAUNCH(w, k_color_recheck_begin, gridFor(d.nBodies), 256, d);
+	LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
+	LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
+	LAUNCH(w, k_block_census, 1, 1024, d, (DState*)nullptr);
+	if (int rc = readState(w)) return rc;
+	s.c = w->h_dstate->c;
+	return 0;
+}
+
+// What the world carries from step to step about its large islands: whether it has had any lately, whether k_block_adopt runs,
+// whether they are too big for the block solvers (the partition is then dissolved), when they are coloured afresh.
+static int largeIslandPolicy(b2hip_world* w, SolveStep& s)
+{
+	DW& d = w->dw;
+	Counters& c = s.c;
+	const bool exact = s.exactLarge;
 	if (c.nLIslands > 0)
 	{
-		if (!largeHint)
+		if (!s.largeHint)
 		{
 			// the first large island after a while: run what was skipped, look again
 			LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
 			LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
 			LAUNCH(w, k_block_census, 1, 1024, d, (DState*)nullptr);
-			rc = readState(w);
-			if (rc) return rc;
+			if (int rc = readState(w)) return rc;
 			c = w->h_dstate->c;
 		}
 		w->largeHintSteps = 120;
@@ -432,745 +449,742 @@ static int phaseSolve(b2hip_world* w)
 	// (newcomers without a home block: from the next step on k_block_adopt hands blocks further, for a while)
 	if (c.nOrphanRows > 0) w->adoptSticky = 16; else if (w->adoptSticky > 0) w->adoptSticky -= 1;
 	w->adoptPasses = w->adoptSticky > 0 && !(w->blocksTooBig && c.nBlocks == 0); // (no partition, none to come: nobody has a block to hand on)
-	const bool plainIslands = d.nJoints == 0 && c.maxDegree <= HUB_DEGREE;
+	s.plainIslands = d.nJoints == 0 && c.maxDegree <= HUB_DEGREE;
 	// ---- large islands that no block solver can take: more constraints than the blocks that fit the device together hold
 	// (1024-lane blocks of ~750 rows: ~190 000; the settled 100 000-box Tumbler has 350 000). They run launch per colour
 	// whatever happens - and a partition would only cost them: it splits the colours into two ranges (interior / cut), 27
 	// colours in use where one range needs 18, and every colour is a launch of every sweep (Tumbler: 6.1 -> 5.2 ms per step).
 	// So the partition is dissolved (all constraints are one class again, coloured afresh once) until the islands have shrunk.
+	const int cap1024 = s.plainIslands ? w->blocksMaxWG : w->sweepMaxWG[2];
+	// (round 6: islands with joints / hubs leave the block sweeps much earlier - k_blocks_sweep is a launch per sweep whose
+	// cut constraints go from workgroup to workgroup through memory, ~45 us per sweep with 256-lane blocks but ~78 us with the
+	// 1024-lane blocks an island above ~60 000 constraints needs, while launch per colour with the top colours as rest
+	// rows and the hub in the same launch has come down to ~70 us there: the Tumbler with 10 000 boxes 1.19 ms per step in
+	// blocks against 1.45 without, with 22 500 boxes 1.92 against 1.61 (profiles/r06_sweep_blocks_crossover.txt))
+	const long long tooBigAt = s.plainIslands ? 800ll * cap1024 : std::min<long long>(800ll * cap1024, w->sweepRowsMax);
+	const long long fitsAgainAt = s.plainIslands ? 650ll * cap1024 : std::min<long long>(650ll * cap1024, (long long)w->sweepRowsMax * 13 / 16);
+	if (!w->blocksTooBig && cap1024 > 0 && c.nLContacts > tooBigAt) w->blocksTooBig = true;
+	else if (w->blocksTooBig && c.nLContacts < fitsAgainAt) w->blocksTooBig = false;
+	if (w->blocksTooBig && c.nBlocks > 0 && !exact && !w->noBlocks)
 	{
-		const int cap1024 = plainIslands ? w->blocksMaxWG : w->sweepMaxWG[2];
-		const bool was = w->blocksTooBig;
-		// (round 6: islands with joints / hubs leave the block sweeps much earlier - k_blocks_sweep is a launch per sweep whose
-		// cut constraints go from workgroup to workgroup through memory, ~45 us per sweep with 256-lane blocks but ~78 us with the
-		// 1024-lane blocks an island above ~60 000 constraints needs, while launch per colour with the top colours as rest
-		// rows and the hub in the same launch has come down to ~70 us there: the Tumbler with 10 000 boxes 1.19 ms per step in
-		// blocks against 1.45 without, with 22 500 boxes 1.92 against 1.61 (profiles/r06_sweep_blocks_crossover.txt))
-		const long long tooBigAt = plainIslands ? 800ll * cap1024 : std::min<long long>(800ll * cap1024, w->sweepRowsMax);
-		const long long fitsAgainAt = plainIslands ? 650ll * cap1024 : std::min<long long>(650ll * cap1024, (long long)w->sweepRowsMax * 13 / 16);
-		if (!w->blocksTooBig && cap1024 > 0 && c.nLContacts > tooBigAt) w->blocksTooBig = true;
-		else if (w->blocksTooBig && c.nLContacts < fitsAgainAt) w->blocksTooBig = false;
-		if (w->blocksTooBig && c.nBlocks > 0 && forceLarge != 2 && !w->noBlocks)
-		{
-			if (w->tracePartition) fprintf(stderr, "[b2hip] partition dissolved: %d constraints in large islands, %d blocks of %d lanes (room for %d)\n", c.nLContacts, c.nBlocks, c.blkLanes, cap1024);
-			const size_t nbAll = w->bodies.size();
-			HIP_TRY(hipMemsetAsync(w->b_blk1.p, 0, nbAll * sizeof(int), w->stream));
-			HIP_TRY(hipMemsetAsync(w->b_adopt.p, 0, nbAll * sizeof(int), w->stream));
-			HIP_TRY(hipMemsetAsync(w->b_adoptStage.p, 0, 3 * nbAll * sizeof(int), w->stream));
-			HIP_TRY(hipMemsetAsync(&w->d_state.p->c.nBlocks, 0, sizeof(int), w->stream));
-			d.serialOrphans = 0; // (no body has a home block now: nothing is an orphan)
-			// the colour census again, under the one class (as after a new partition), then every colour afresh
-			LAUNCH(w, k_color_recheck_begin, gridFor(d.nBodies), 256, d);
-			LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
-			LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
-			LAUNCH(w, k_block_census, 1, 1024, d, (DState*)nullptr);
-			rc = readState(w);
-			if (rc) return rc;
-			c = w->h_dstate->c;
-			c.needRecolor = 1;
-			colorSmallQueued = false;
-		}
-		(void)was;
-		// Without a partition every colour is a launch of every sweep, and colours handed out one new contact at a time creep
-		// up (24 in use on the settled Tumbler where a colouring from scratch needs 19 - five colours are 0.3 ms of its step):
-		// every 64th step the island is coloured afresh.
-		// (round 5: ... if they HAVE crept up - more than two colours above what the last colouring from scratch needed; the
-		// top colours of a sweep are hops of k_large_rest now, ~2.5 us each, and a colouring from scratch is 5 ms of claim /
-		// resolve rounds with read-backs: the settled Tumbler's step 64, 128, ... took 9 - 11 ms against 4)
-		if (w->blocksTooBig && forceLarge != 2 && !w->noBlocks && c.nLIslands > 0)
-		{
-			if (w->recolorCountdown <= 0)
-			{
-				// (a colouring from scratch lands anywhere between the busiest plain body's degree + 1 and + 8: the measure is the
-				// better of what the last one reached and degree + 3, so that a poor one is not kept as the yardstick)
-				const int yard = std::min(w->freshColors, c.maxDegreePlain + 3);
-				if (w->freshColors <= 0 || w->recolorSlack < 0 || c.nColors > yard + w->recolorSlack)
-				{
-					c.needRecolor = 1;
-					colorSmallQueued = false;
-					w->freshColorsPending = true;
-					w->recolorCountdown = 64;
-				}
-				else w->recolorCountdown = 16;
-			}
-			w->recolorCountdown -= 1;
-		}
-		else { w->recolorCountdown = 0; w->freshColors = 0; }
+		if (w->tracePartition) fprintf(stderr, "[b2hip] partition dissolved: %d constraints in large islands, %d blocks of %d lanes (room for %d)\n", c.nLContacts, c.nBlocks, c.blkLanes, cap1024);
+		const size_t nbAll = w->bodies.size();
+		HIP_TRY(hipMemsetAsync(w->b_blk1.p, 0, nbAll * sizeof(int), w->stream));
+		HIP_TRY(hipMemsetAsync(w->b_adopt.p, 0, nbAll * sizeof(int), w->stream));
+		HIP_TRY(hipMemsetAsync(w->b_adoptStage.p, 0, 3 * nbAll * sizeof(int), w->stream));
+		HIP_TRY(hipMemsetAsync(&w->d_state.p->c.nBlocks, 0, sizeof(int), w->stream));
+		d.serialOrphans = 0; // (no body has a home block now: nothing is an orphan)
+		// the colour census again, under the one class (as after a new partition), then every colour afresh
+		if (int rc = recheckColors(w, s)) return rc;
+		c.needRecolor = 1;
+		s.colorSmallQueued = false;
 	}
+	// Without a partition every colour is a launch of every sweep, and colours handed out one new contact at a time creep
+	// up (24 in use on the settled Tumbler where a colouring from scratch needs 19 - five colours are 0.3 ms of its step):
+	// every 64th step the island is coloured afresh.
+	// (round 5: ... if they HAVE crept up - more than two colours above what the last colouring from scratch needed; the
+	// top colours of a sweep are hops of k_large_rest now, ~2.5 us each, and a colouring from scratch is 5 ms of claim /
+	// resolve rounds with read-backs: the settled Tumbler's step 64, 128, ... took 9 - 11 ms against 4)
+	if (w->blocksTooBig && !exact && !w->noBlocks && c.nLIslands > 0)
+	{
+		if (w->recolorCountdown <= 0)
+		{
+			// (a colouring from scratch lands anywhere between the busiest plain body's degree + 1 and + 8: the measure is the
+			// better of what the last one reached and degree + 3, so that a poor one is not kept as the yardstick)
+			const int yard = std::min(w->freshColors, c.maxDegreePlain + 3);
+			if (w->freshColors <= 0 || c.nColors > yard + RECOLOR_SLACK)
+			{
+				c.needRecolor = 1;
+				s.colorSmallQueued = false;
+				w->freshColorsPending = true;
+				w->recolorCountdown = 64;
+			}
+			else w->recolorCountdown = 16;
+		}
+		w->recolorCountdown -= 1;
+	}
+	else { w->recolorCountdown = 0; w->freshColors = 0; }
 	// (from the next step on: in islands with joints / hubs the constraints of such newcomers are swept in order instead)
-	w->serialOrphansNext = (forceLarge != 2 && !w->noBlocks && !w->noSweepBlocks && !w->blocksTooBig && c.nBlocks > 0 && (d.nJoints > 0 || c.maxDegree > HUB_DEGREE)) ? 1 : 0;
-	// ---- block partition of the large islands: (re)made when bodies without a home block joined, when a block outgrew a
-	// workgroup, or when too many constraints cross block boundaries (the pile has moved since the partition was made)
-	// (islands with joints or hub bodies are partitioned too: k_blocks_sweep does their contact sweeps block-wise, one launch
-	// per sweep, between the joint walks and the hub sweeps)
-	const bool blockShape = forceLarge != 2 && !w->noBlocks && !w->blocksTooBig && c.nLIslands > 0 && (plainIslands || !w->noSweepBlocks) &&
-		(sp.warmStarting ? 1 : 0) + sp.velIters > 0 && w->blocksMaxWG > 0;
-	if (blockShape && c.partitionCooldown == 0)
-	{
-		// Block size: one 1024-lane block while the large islands fit it (nothing ever goes through memory then), else
-		// 256-lane blocks (measured on the 10 011-box pyramid: 215 us against 235 / 245 us with 512 / 1024 lanes - the
-		// workgroup barriers of the interior colours are cheaper and the position solves spread over more CUs)
-		// (512 lanes once 256-lane blocks would be more than fit the device together)
-		// (... and 1024 again once 512-lane blocks would not)
-		auto lanesFor = [w](const Counters& k) { return w->blockLanes ? w->blockLanes : (k.nLContacts <= 900 ? 1024 : (k.nLContacts > 400 * w->blocksMaxWG ? 1024 : (k.nLContacts > 200 * w->blocksMaxWG ? 512 : 256))); };
-		auto misfit = [](const Counters& k) { return k.nBlocks == 0 || k.nOrphanRows > 0 || k.blkMaxRows > k.blkLanes || k.blkMaxBodies > k.blkLanes || k.nSerialOrphans > 2048; };
-		bool need = misfit(c) || (c.partitionAge > 240 && (4 * c.nCutRows > c.nLContacts || (c.blkLanes != lanesFor(c) && 2 * c.nLContacts < 900)));
-		int lanes = lanesFor(c);
-		int target = BLOCK_TARGET_DEG * lanes / BLOCK_LANES;
-		// (the last partition did not last - a growing pile: leave the blocks room for the bodies they will adopt, if half as
-		// many blocks again still fit the device together)
-		{
-			const int cap = plainIslands ? w->blocksMaxWG : (lanes == 512 ? w->sweepMaxWG[1] : (lanes == BLOCK_LANES ? w->sweepMaxWG[2] : w->sweepMaxWG[0]));
-			if (c.nBlocks > 0 && c.partitionAge < 16 && c.nBlocks * 3 / 2 + 8 <= cap) target = target * 2 / 3;
-			if (w->tracePartition) fprintf(stderr, "[b2hip] capacity for %d-lane blocks: %d\n", lanes, cap);
-		}
-		for (int attempt = 0; need && attempt < 3; ++attempt)
-		{
-			if (w->tracePartition)
-				fprintf(stderr, "[b2hip] partition (attempt %d, target %d, lanes %d): blocks %d orphan rows %d max rows %d max bodies %d lanes %d age %d cut %d of %d\n",
-					attempt, target, lanes, c.nBlocks, c.nOrphanRows, c.blkMaxRows, c.blkMaxBodies, c.blkLanes, c.partitionAge, c.nCutRows, c.nLContacts);
-			HIP_TRY(hipMemcpyAsync(&w->d_state.p->c.blkLanes, &lanes, sizeof(int), hipMemcpyHostToDevice, w->stream));
-			rc = partitionLargeIslands(w, target);
-			if (rc) return rc;
-			colorSmallQueued = false; // (the colours are checked against the new partition: what is open after that is new work)
-			rc = readState(w);
-			if (rc) return rc;
-			c = w->h_dstate->c;
-			need = misfit(c);
-			target = target * 2 / 3;
-		}
-		if (need)
-		{
-			// does not fit (e.g. more blocks than workgroups can be resident): back to the other solvers for a while
-			const int cooldown = 120;
-			HIP_TRY(hipMemcpyAsync(&w->d_state.p->c.partitionCooldown, &cooldown, sizeof(int), hipMemcpyHostToDevice, w->stream));
-			HIP_TRY(hipStreamSynchronize(w->stream));
-		}
-	}
+	w->serialOrphansNext = (!exact && !w->noBlocks && !w->noSweepBlocks && !w->blocksTooBig && c.nBlocks > 0 && (d.nJoints > 0 || c.maxDegree > HUB_DEGREE)) ? 1 : 0;
+	return 0;
+}
 
-	stampPhase(w, 4);
-	const bool exactLarge = forceLarge == 2;
-	bool hasHubs = !exactLarge && (c.maxDegree > HUB_DEGREE || c.nSerialOrphans > 0); // (anything for k_large_hub)
-	// Small and large islands share nothing (different bodies, contacts, island tables): when both tiers are present the
-	// small-island chain (DFS order, chunking, k_solve_small) runs on a side stream beside the large-island solver and
-	// joins before SynchronizeFixtures. With a handful of small islands that chain is one or two workgroups of big kernels
-	// whose cost is instruction fetch from a cold cache (~2 us per KB of code executed: 83 us for a dozen free bodies next
-	// to the 10k-body pyramid) - time the large solver's resident grid leaves plenty of idle CUs for.
-	bool sideStream = false;
-	bool smallDeferred = false;
-	// (the launches of the small-island chain; on the side stream they are issued AFTER the large-island solver's own
-	// launches - the solver is what the step waits for, and every launch the host makes first delays it by ~3 us)
-	auto launchSmallIslands = [&](hipStream_t ss) -> int
+// ---- block partition of the large islands: (re)made when bodies without a home block joined, when a block outgrew a
+// workgroup, or when too many constraints cross block boundaries (the pile has moved since the partition was made)
+// (islands with joints or hub bodies are partitioned too: k_blocks_sweep does their contact sweeps block-wise, one launch
+// per sweep, between the joint walks and the hub sweeps)
+static int repartition(b2hip_world* w, SolveStep& s)
+{
+	const StepParams& sp = w->sp;
+	Counters& c = s.c;
+	s.blockShape = !s.exactLarge && !w->noBlocks && !w->blocksTooBig && c.nLIslands > 0 && (s.plainIslands || !w->noSweepBlocks) &&
+		(sp.warmStarting ? 1 : 0) + sp.velIters > 0 && w->blocksMaxWG > 0;
+	if (!s.blockShape || c.partitionCooldown != 0) return 0;
+	// Block size: one 1024-lane block while the large islands fit it (nothing ever goes through memory then), else
+	// 256-lane blocks (measured on the 10 011-box pyramid: 215 us against 235 / 245 us with 512 / 1024 lanes - the
+	// workgroup barriers of the interior colours are cheaper and the position solves spread over more CUs)
+	// (512 lanes once 256-lane blocks would be more than fit the device together)
+	// (... and 1024 again once 512-lane blocks would not)
+	auto lanesFor = [w](const Counters& k) { return w->blockLanes ? w->blockLanes : (k.nLContacts <= 900 ? 1024 : (k.nLContacts > 400 * w->blocksMaxWG ? 1024 : (k.nLContacts > 200 * w->blocksMaxWG ? 512 : 256))); };
+	auto misfit = [](const Counters& k) { return k.nBlocks == 0 || k.nOrphanRows > 0 || k.blkMaxRows > k.blkLanes || k.blkMaxBodies > k.blkLanes || k.nSerialOrphans > 2048; };
+	bool need = misfit(c) || (c.partitionAge > 240 && (4 * c.nCutRows > c.nLContacts || (c.blkLanes != lanesFor(c) && 2 * c.nLContacts < 900)));
+	int lanes = lanesFor(c);
+	int target = BLOCK_TARGET_DEG * lanes / BLOCK_LANES;
+	// (the last partition did not last - a growing pile: leave the blocks room for the bodies they will adopt, if half as
+	// many blocks again still fit the device together)
 	{
-		if (sideStream && !poll) HIP_TRY(hipStreamWaitEvent(ss, w->evFork, 0));
-		LAUNCH_ON(w, ss, k_island_dfs, gridFor(c.nSIslands, 64, 1 << 20), 64, d);
-		if (!sideStream) stampPhase(w, 5);
-		if (!exactLarge)
-		{
-			const bool timeIt = w->kernelTiming == 1 && c.nLIslands == 0;
-			if (timeIt) { int rck = ktRecord(w); if (rck) return rck; w->ktKind = 2; }
-			if (c.nSmallJointed > 0)
-			{
-				if (c.chunkLanes == TINY_CHUNK_LANES) LAUNCH_ON(w, ss, (k_solve_small<TINY_CHUNK_LANES, true>), c.nChunks, TINY_CHUNK_LANES, d, sp);
-				else LAUNCH_ON(w, ss, (k_solve_small<SMALL_CHUNK_LANES, true>), c.nChunks, SMALL_CHUNK_LANES, d, sp);
-			}
-			else if (c.chunkLanes == TINY_CHUNK_LANES) LAUNCH_ON(w, ss, (k_solve_small<TINY_CHUNK_LANES, false>), c.nChunks, TINY_CHUNK_LANES, d, sp);
-			else LAUNCH_ON(w, ss, (k_solve_small<SMALL_CHUNK_LANES, false>), c.nChunks, SMALL_CHUNK_LANES, d, sp);
-			if (timeIt) { int rck = ktRecord(w); if (rck) return rck; }
-		}
-		if (sideStream) HIP_TRY(hipEventRecord(w->evJoin, ss));
-		else stampPhase(w, 6);
-		return 0;
-	};
-	if (c.nSIslands > 0)
-	{
-		sideStream = !exactLarge && c.nLIslands > 0 && !w->debugTrace && !w->kernelTimingLaunches && !w->noSideStream;
-		if (sideStream)
-		{
-			// fork here (the side stream needs the island build, nothing of the large-island solver); launches later.
-			// With the census polled the host has SEEN the island build finish (the publication is its last act): the side
-			// stream needs no event to wait for - an event record is a packet of its own on the main stream, ~6 us between
-			// the colouring and the solver
-			if (!poll) HIP_TRY(hipEventRecord(w->evFork, w->stream));
-			smallDeferred = true;
-			stampPhase(w, 5);
-			stampPhase(w, 6);
-		}
-		else
-		{
-			rc = launchSmallIslands(w->stream);
-			if (rc) return rc;
-		}
+		const int cap = s.plainIslands ? w->blocksMaxWG : (lanes == 512 ? w->sweepMaxWG[1] : (lanes == BLOCK_LANES ? w->sweepMaxWG[2] : w->sweepMaxWG[0]));
+		if (c.nBlocks > 0 && c.partitionAge < 16 && c.nBlocks * 3 / 2 + 8 <= cap) target = target * 2 / 3;
+		if (w->tracePartition) fprintf(stderr, "[b2hip] capacity for %d-lane blocks: %d\n", lanes, cap);
 	}
-	else
+	for (int attempt = 0; need && attempt < 3; ++attempt)
+	{
+		if (w->tracePartition)
+			fprintf(stderr, "[b2hip] partition (attempt %d, target %d, lanes %d): blocks %d orphan rows %d max rows %d max bodies %d lanes %d age %d cut %d of %d\n",
+				attempt, target, lanes, c.nBlocks, c.nOrphanRows, c.blkMaxRows, c.blkMaxBodies, c.blkLanes, c.partitionAge, c.nCutRows, c.nLContacts);
+		HIP_TRY(hipMemcpyAsync(&w->d_state.p->c.blkLanes, &lanes, sizeof(int), hipMemcpyHostToDevice, w->stream));
+		if (int rc = partitionLargeIslands(w, target)) return rc;
+		s.colorSmallQueued = false; // (the colours are checked against the new partition: what is open after that is new work)
+		if (int rc = readState(w)) return rc;
+		c = w->h_dstate->c;
+		need = misfit(c);
+		target = target * 2 / 3;
+	}
+	if (need)
+	{
+		// does not fit (e.g. more blocks than workgroups can be resident): back to the other solvers for a while
+		const int cooldown = 120;
+		HIP_TRY(hipMemcpyAsync(&w->d_state.p->c.partitionCooldown, &cooldown, sizeof(int), hipMemcpyHostToDevice, w->stream));
+		HIP_TRY(hipStreamSynchronize(w->stream));
+	}
+	return 0;
+}
+
+// The launches of the small-island chain (DFS order, chunking, k_solve_small) on `ss`: the main stream or the side stream.
+static int launchSmallIslands(b2hip_world* w, const SolveStep& s, hipStream_t ss)
+{
+	DW& d = w->dw;
+	const StepParams& sp = w->sp;
+	const Counters& c = s.c;
+	if (s.sideStream && !s.poll) HIP_TRY(hipStreamWaitEvent(ss, w->evFork, 0));
+	LAUNCH_ON(w, ss, k_island_dfs, gridFor(c.nSIslands, 64, 1 << 20), 64, d);
+	if (!s.sideStream) stampPhase(w, 5);
+	if (!s.exactLarge)
+	{
+		const bool timeIt = w->kernelTiming == 1 && c.nLIslands == 0;
+		if (timeIt) { int rck = ktRecord(w); if (rck) return rck; w->ktKind = 2; }
+		if (c.nSmallJointed > 0)
+		{
+			if (c.chunkLanes == TINY_CHUNK_LANES) LAUNCH_ON(w, ss, (k_solve_small<TINY_CHUNK_LANES, true>), c.nChunks, TINY_CHUNK_LANES, d, sp);
+			else LAUNCH_ON(w, ss, (k_solve_small<SMALL_CHUNK_LANES, true>), c.nChunks, SMALL_CHUNK_LANES, d, sp);
+		}
+		else if (c.chunkLanes == TINY_CHUNK_LANES) LAUNCH_ON(w, ss, (k_solve_small<TINY_CHUNK_LANES, false>), c.nChunks, TINY_CHUNK_LANES, d, sp);
+		else LAUNCH_ON(w, ss, (k_solve_small<SMALL_CHUNK_LANES, false>), c.nChunks, SMALL_CHUNK_LANES, d, sp);
+		if (timeIt) { int rck = ktRecord(w); if (rck) return rck; }
+	}
+	if (s.sideStream) HIP_TRY(hipEventRecord(w->evJoin, ss));
+	else stampPhase(w, 6);
+	return 0;
+}
+
+// Small and large islands share nothing (different bodies, contacts, island tables): when both tiers are present the
+// small-island chain runs on a side stream beside the large-island solver and joins before SynchronizeFixtures. With a
+// handful of small islands that chain is one or two workgroups of big kernels whose cost is instruction fetch from a cold
+// cache (~2 us per KB of code executed: 83 us for a dozen free bodies next to the 10k-body pyramid) - time the large
+// solver's resident grid leaves plenty of idle CUs for.
+// (On the side stream the launches are issued AFTER the large-island solver's own first launches - the solver is what the
+// step waits for, and every launch the host makes first delays it by ~3 us: s.smallDeferred.)
+static int solveSmallIslands(b2hip_world* w, SolveStep& s)
+{
+	if (s.c.nSIslands == 0)
 	{
 		stampPhase(w, 5);
 		stampPhase(w, 6);
-	}
-	int nColors = 0;
-	int nLIslands = c.nLIslands, nLBodies = c.nLBodies, nLContacts = c.nLContacts;
-	if (exactLarge && c.nSIslands > 0)
-	{
-		// exact-order mode: colours := dependency levels of the reference's own constraint order
-		LAUNCH(w, k_exact_begin, gridFor(c.nSContacts + 1), 256, d);
-		LAUNCH(w, k_exact_convert, gridFor(std::max(c.nSContacts, c.nSBodies)), 256, d);
-		rc = readState(w);
-		if (rc) return rc;
-		nColors = w->h_dstate->c.nColors;
-		nLIslands = c.nSIslands;
-		nLBodies = c.nSBodies;
-		nLContacts = c.nSContacts;
-	}
-	if (nLIslands > 0)
-	{
-		const int gB = gridFor(nLBodies), gC = gridFor(std::max(nLContacts, 1));
-		nColors = exactLarge ? nColors : c.nColors;
-		const bool hasJoints = d.nJoints > 0;
-		// k_solve_dataflow: two waves per workgroup while that still leaves at most ~2 workgroups per CU (a hand-off is
-		// priced by the consumer CU's memory queue: 256 -> 128 lanes took the 10k-body pyramid from 464 to 409 us; 64 lanes
-		// lost it again to the grid barriers), four waves for bigger islands
-		const int dfLanes = w->dfLanesForced ? w->dfLanesForced : (nLContacts <= 128 * 2 * w->nCU ? 128 : PERSIST_LANES);
-		const int persistLanes = w->solverBarriers ? PERSIST_LANES : dfLanes;
-		const int persistWG = (nLContacts + persistLanes - 1) / persistLanes;
-		const int persistMaxWG = w->persistMaxWG * (PERSIST_LANES / persistLanes);
-		bool usePersistent = !exactLarge && !hasJoints && !hasHubs && !w->debugTrace && !w->kernelTimingLaunches &&
-			persistMaxWG > 0 && persistWG <= persistMaxWG;
-		// the block solver (bodies in LDS, one workgroup per block of the partition): whenever the partition fits
-		const bool partitionFits = blockShape && c.nBlocks > 0 && c.nOrphanRows == 0 && c.blkMaxRows <= c.blkLanes && c.blkMaxBodies <= c.blkLanes;
-		bool useBlocks = usePersistent && partitionFits && plainIslands && !w->solverBarriers && !w->solverRows && !w->solverMailbox &&
-			c.nBlocks <= w->blocksMaxWG &&
-			(sp.velIters + 2) * (MAX_COLORS + 1) < 65536 && (sp.posIters + 1) * (MAX_COLORS + 1) < 65536;
-		// one launch per sweep over the same blocks for islands that need joint walks / hub sweeps in between
-		const int sweepMaxWG = c.blkLanes == 512 ? w->sweepMaxWG[1] : (c.blkLanes == BLOCK_LANES ? w->sweepMaxWG[2] : w->sweepMaxWG[0]);
-		bool useSweep = !useBlocks && !exactLarge && partitionFits && !plainIslands && !w->debugTrace && !w->kernelTimingLaunches &&
-			c.nBlocks <= sweepMaxWG;
-		d.blockSort = (useBlocks || useSweep) ? 1 : 0;
-		bool useResident = usePersistent && (useBlocks || B2HIP_HAVE_VALIDATION_SOLVERS);
-		bool colorsOnDevice = false;
-		bool censusVoid = false;
-		bool colorSpill = false; // some constraint found no free colour this step: it sits in the hub group and is swept in order
-		bool roundsToo = false;  // the grid-wide colouring rounds run (asked for by the census, or to finish what k_color_small left)
-		if (!exactLarge && (c.needRecolor || c.nUncolored > 0 || c.nCompact > 0))
-		{
-			if (!c.needRecolor && c.nUncolored <= COLOR_SMALL_MAX)
-			{
-				// the usual case (a few new contacts on a settled island, a colour class to compact): one workgroup colours
-				// them; the resident solver reads the colour count from the device, the launch-per-colour path reads it back
-				// (the launch-per-colour path needs the colour count: published by the kernel and polled - a copy + synchronise
-				// otherwise, B2HIP_NO_CENSUS_POLL=1)
-				const bool pubColors = poll && !useResident && !w->colorAheadOff;
-				if (!colorSmallQueued)
-				{
-					if (pubColors) w->pubSeq2 = (w->pubSeq2 + 1) & 0x3fffffff;
-					LAUNCH(w, k_color_small, 1, 1024, d, 0, 0, pubColors ? w->d_pub2 : (DState*)nullptr, w->pubSeq2); // (else: it went out behind the census)
-				}
-				if (useResident)
-				{
-					colorsOnDevice = true;
-					w->colorSmallPending = true;
-				}
-				else
-				{
-					if ((colorSmallQueued && colorAheadPublished) || (!colorSmallQueued && pubColors))
-					{
-						rc = awaitColors(w);
-						if (rc == 0) c.nColors = w->h_dstate->c.nColors;
-						if (rc == 0) memcpy(c.colorRows, w->h_dstate->c.colorRows, sizeof(c.colorRows));
-					}
-					else rc = readState(w);
-					if (rc) return rc;
-					nColors = w->h_dstate->c.nColors;
-					// (round 6: neither ends the step any more. A constraint without a free colour on its two bodies is swept in order
-					// with the hub rows - k_hub_flag; rounds that did not converge are finished by the grid-wide rounds below)
-					if (w->h_dstate->c.overflow & 4) { if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "more than 64 constraint colours on one body"); colorSpill = true; }
-					if (w->h_dstate->c.nUncolored != 0)
-					{
-						if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "incremental colouring did not converge");
-						roundsToo = true;
-						c.nUncolored = w->h_dstate->c.nUncolored;
-						w->colorRecoveries += 1;
-						if (getenv("B2HIP_TRACE_RECOVERY")) fprintf(stderr, "[b2hip] k_color_small left %d constraints without a colour: the grid-wide rounds finish\n", c.nUncolored);
-					}
-				}
-			}
-			else roundsToo = true;
-			if (roundsToo)
-			{
-			// a colour clash on some body -> colour the large islands from scratch; otherwise only the
-			// constraints that have no colour yet join the Jones-Plassmann rounds (existing masks stay)
-			censusVoid = true; // (thousands of constraints get their colours now: the colour census of this step is history)
-			int uncolored = c.nUncolored;
-			if (c.needRecolor)
-			{
-				LAUNCH(w, k_color_begin, gridFor(d.capContacts), 256, d);
-				uncolored = nLContacts; // upper bound (hub constraints excluded on the device); refreshed by the read-back below
-			}
-			int batch = c.needRecolor ? 8 : 2;
-			while (uncolored > 0)
-			{
-				for (int r = 0; r < batch; ++r)
-				{
-					LAUNCH(w, k_color_claim, gC, 256, d);
-					LAUNCH(w, k_color_resolve, gC, 256, d);
-				}
-				rc = readState(w);
-				if (rc) return rc;
-				uncolored = w->h_dstate->c.nUncolored;
-				nColors = w->h_dstate->c.nColors;
-				if (w->h_dstate->c.overflow & 4) { if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "more than 64 constraint colours on one body"); colorSpill = true; }
-				batch = 8;
-			}
-			if (w->freshColorsPending) { w->freshColors = nColors < 63 ? nColors : 63; w->freshColorsPending = false; }
-			}
-		}
-		if (colorSpill) w->colorRecoveries += 1;
-		// (a constraint without a colour carries HUB_COLOR: the colours to launch end below it)
-		if (!exactLarge && nColors > HUB_COLOR) nColors = HUB_COLOR;
-		// ---- the row layout and the solver proper, as ONE unit that can run a second time in its SAFE form (round 6, VERDICT r05
-		// item 5): b2World::Step has no failure path (b2World.cpp:1613-1710), and a wait between workgroups that times out - a
-		// co-tenant on the device, a workgroup that was not resident - used to fail the step and leave a dead world. The unit
-		// saves what the solver changes (k_solver_snapshot: rows of the large islands' bodies, impulses and flags of their
-		// contacts, their joints) before its first solver launch; behind its last one a one-lane kernel publishes the overflow
-		// word, the host looks at it (a poll of mapped memory: ~5 us with the next launch's latency - only where the unit used a
-		// kernel whose workgroups wait for one another), and on a timed-out wait puts the saved state back and runs the unit
-		// again on the plain path: rows by colour, a launch per colour, tail colours and hub rows in k_sweep_end's ONE workgroup -
-		// nothing in it waits for another workgroup. Same colouring, same arithmetic, same order on every body: the bits the
-		// fast path would have produced (tests/test_gpu_recovery.py).
-		bool waitsBetweenWorkgroups = false;
-		auto runLarge = [&](const bool safe) -> int
-		{
-		if (safe)
-		{
-			usePersistent = useBlocks = useSweep = useResident = false;
-			colorsOnDevice = false;
-			d.blockSort = 0;
-		}
-		if (colorSpill) hasHubs = true; // (k_hub_flag lists the constraints that found no colour)
-		if (!d.blockSort) LAUNCH(w, k_color_scan, 1, 64, d); // (segments by colour: the block solvers sort their rows themselves)
-		// ---- the end of every sweep without a launch per colour (b2d_kernels_sweep_end.h). The REST colours - from the highest
-		// colour down while this step's colour census (k_color_check, published with the island census) keeps them below
-		// restRowsMax rows together - are swept by ONE launch of k_large_rest, as data flow per body; k_color_fill notes them
-		// on their bodies. Which colours are "rest" changes nothing in the result (the order on every body is the launches'):
-		// a launch-count matter. Not on a step that colours afresh: its census is void.
-		const bool useSweepEnd = w->sweepEnd && !exactLarge && !w->debugTrace;
-		int restFirst = 0x7fffffff; // (none)
-		if (useSweepEnd && w->restFlow && !safe && !d.blockSort && !c.needRecolor && !censusVoid && nColors > 0 && nColors < MAX_COLORS)
-		{
-			long long sum = 0;
-			int t = nColors;
-			while (t > 0 && sum + c.colorRows[t - 1] <= (long long)w->restRowsMax)
-			{
-				sum += c.colorRows[t - 1];
-				t -= 1;
-			}
-			if (nColors - t >= 2) restFirst = t;
-		}
-		w->lastRestFirst = restFirst < nColors ? restFirst : nColors;
-		LAUNCH(w, k_color_fill, gC, 256, d, restFirst < MAX_COLORS ? restFirst : MAX_COLORS);
-		// (round 6: one single-workgroup launch sorts the hub group's segment of the row array in place - k_hub_build - where the
-		// last step's list was short enough for its keys to sit in LDS; the four launches below otherwise)
-		const bool hubBuildOne = hasHubs && !w->noHubBuild && w->last.nHubRows <= HUB_BUILD_LDS;
-		if (hubBuildOne)
-		{
-			LAUNCH(w, k_hub_build, 1, 1024, d, d.hubWide ? 1 : 0, (!w->noHubOrder && (d.hubWide || w->hubOrderAll)) ? 1 : 0, d.blockSort ? 1 : 0);
-			w->hubSteps += 1;
-		}
-		else if (hasHubs)
-		{
-			// the hub constraints in contact-index order (deterministic whatever the atomics of k_color_fill did)
-			LAUNCH(w, k_hub_flag, gridFor(d.capContacts), 256, d);
-			deviceExclusiveScan<int>(w->stream, d.keepFlag, d.keepScan, d.scanTmp, w->scanCtx, &d.st->c.nContacts, d.capContacts);
-			LAUNCH(w, k_hub_fill, gridFor(d.capContacts), 256, d);
-			// (the hub meets its partners in the order of their highest colour: b2d_kernels_solve_large.h, k_hub_order)
-			if (!w->noHubOrder && (d.hubWide || w->hubOrderAll)) LAUNCH(w, k_hub_order, 1, 1024, d, d.hubWide ? 0 : 1);
-			w->hubSteps += 1;
-		}
-		stampPhase(w, 7);
-		const int gK = gridFor(std::max(nLContacts / std::max(nColors, 1), 1) * 2);
-		// A colour launch is a chain of dependent loads per lane (~4.5 us whatever it holds): a lane that makes a second trip
-		// of the grid-stride loop pays the chain twice - the Tumbler's five biggest colours (41 000 - 42 000 rows against a grid
-		// of 39 000 lanes sized from the MEAN colour) took 8 us instead of 6. Sized per colour from this step's census now
-		// (+ what k_color_small may still add), in workgroups of colorLanes lanes so that the rows spread over all CUs.
-		const int kLanes = w->colorLanes;
-		const bool censusGrid = !exactLarge && nColors > 0 && nColors <= MAX_COLORS && !c.needRecolor && !censusVoid && !w->noCensusGrid;
-		auto gridOfColor = [&](int col) -> int
-		{
-			if (!censusGrid || col < 0 || col >= MAX_COLORS) return gK;
-			return gridFor((size_t)c.colorRows[col] + 512, kLanes, 1 << 16);
-		};
-		const int gJ = gridFor(std::max(nLIslands, 1), 64, 1 << 16);
-		waitsBetweenWorkgroups = useResident || useSweep || (useSweepEnd && restFirst < nColors);
-		if (!safe && w->recoverOn && waitsBetweenWorkgroups) LAUNCH(w, k_solver_snapshot, gridFor(std::max(nLBodies, nLContacts)), 256, d, 0);
-		if (useResident)
-		{
-			// one resident grid for the whole sweep structure; colour boundaries are grid barriers (validation_src/b2d_validation_solvers.h)
-			// (the barrier words were zeroed by k_step_begin: one resident launch per step)
-			if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; w->ktKind = useBlocks ? 4 : 3; }
-			const int nColorsArg = colorsOnDevice ? -1 : nColors; // -1: read Counters::nColors on the device
-			if (useBlocks)
-			{
-				// (tags carry a 15-bit epoch: wipe the exchange rows when it comes round, like the mailbox slots below)
-				if ((w->dfEpoch >> 14) != w->dfWipedAt)
-				{
-					HIP_TRY(hipMemsetAsync(w->b_cutv.p, 0, w->b_cutv.cap * sizeof(float4), w->stream));
-					HIP_TRY(hipMemsetAsync(w->b_posv.p, 0, w->b_posv.cap * sizeof(float4), w->stream));
-					HIP_TRY(hipMemsetAsync(w->dfInbox.p, 0, w->dfInbox.cap * sizeof(float4), w->stream));
-					w->dfWipedAt = w->dfEpoch >> 14;
-				}
-				if (c.blkLanes == 512) LAUNCH(w, k_solve_blocks<512>, c.nBlocks, 512, d, sp, w->gridBar.p, w->dfEpoch);
-				else if (c.blkLanes == 256) LAUNCH(w, k_solve_blocks<256>, c.nBlocks, 256, d, sp, w->gridBar.p, w->dfEpoch);
-				else if (c.blkLanes == BLOCK_LANES) LAUNCH(w, k_solve_blocks<BLOCK_LANES>, c.nBlocks, BLOCK_LANES, d, sp, w->gridBar.p, w->dfEpoch);
-				else return setError(B2HIP_ERR_INVALID, "block partition made for an unknown workgroup size");
-				w->dfEpoch += 1;
-				w->blockSteps += 1;
-				w->blocksThisStep = true;
-			}
-#if B2HIP_HAVE_VALIDATION_SOLVERS
-			else if (w->solverBarriers) LAUNCH(w, k_solve_persistent, persistWG, PERSIST_LANES, d, sp, nColorsArg, w->gridBar.p);
-			else if (w->solverRows || (sp.velIters + 2) * DF_RANKS >= 65536 || (sp.posIters + 1) * DF_RANKS >= 65536)
-				LAUNCH(w, k_solve_dataflow, persistWG, persistLanes, d, sp, nColorsArg, w->gridBar.p, w->dfSleep);
-			else
-			{
-				// optional single-XCD attempt first when the island fits one XCD's CUs (k_solve_mailbox<true>), then the ordinary
-				// launch, which returns at once if the attempt took the step
-				const int xcdWG = persistMaxWG / 8;
-				const bool tryLocal = w->solverLocal && persistWG <= xcdWG;
-				// the 15-bit epoch of the mailbox tags comes round every 16 384 steps: wipe the slots then, so that a slot
-				// nobody has written since cannot carry a matching tag
-				if (w->dfEpoch != 0 && (w->dfEpoch & 0x3fff) == 0)
-				{
-					HIP_TRY(hipMemsetAsync(w->dfInbox.p, 0, w->dfInbox.cap * sizeof(float4), w->stream));
-					HIP_TRY(hipMemsetAsync(w->b_cutv.p, 0, w->b_cutv.cap * sizeof(float4), w->stream));
-				}
-				if (tryLocal) LAUNCH(w, k_solve_mailbox<true>, 8 * persistWG, persistLanes, d, sp, nColorsArg, w->gridBar.p, w->dfEpoch, persistWG, 0);
-				LAUNCH(w, k_solve_mailbox<false>, persistWG, persistLanes, d, sp, nColorsArg, w->gridBar.p, w->dfEpoch, persistWG, tryLocal ? 1 : 0);
-				w->dfEpoch += 1;
-			}
-#endif
-			if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; }
-			w->persistSteps += 1;
-			if (smallDeferred) { smallDeferred = false; rc = launchSmallIslands(w->stream2); if (rc) return rc; }
-		}
-		else
-		{
-		if (smallDeferred) { smallDeferred = false; rc = launchSmallIslands(w->stream2); if (rc) return rc; }
-		TRACE("before_integrate");
-		if (w->debugTrace)
-		{
-			const size_t nb = w->bodies.size();
-			(void)w->dbgPreVel.ensure(nb, w->stream); (void)w->dbgVel.ensure(nb, w->stream); (void)w->dbgLi.ensure(nb + 64, w->stream);
-			HIP_TRY(hipMemcpyAsync(w->dbgPreVel.p, w->b_vel.p, nb * 16, hipMemcpyDeviceToDevice, w->stream));
-			HIP_TRY(hipMemcpyAsync(w->dbgLi.p, w->li_bodies.p, nb * 4, hipMemcpyDeviceToDevice, w->stream));
-			HIP_TRY(hipMemcpyAsync(w->dbgLi.p + nb, &w->d_state.p->c, 64 * 4 > sizeof(Counters) ? sizeof(Counters) : 64 * 4, hipMemcpyDeviceToDevice, w->stream));
-		}
-		// (timing mode 5: ONE event pair around the whole large-island solver family of the launch-per-colour path - integrate,
-		// constraint set-up, every sweep, impulses stored, positions, write-back and sleep)
-		if (w->kernelTiming == 5 && !safe) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 8; w->familyLaunchesAtStart = w->launchCount; }
-		const bool sortInIntegrate = hasJoints && !exactLarge && !w->debugTrace;
-		LAUNCH(w, k_large_integrate, gB, 256, d, sp, sortInIntegrate ? 1 : 0);
-		if (w->debugTrace) HIP_TRY(hipMemcpyAsync(w->dbgVel.p, w->b_vel.p, w->bodies.size() * 16, hipMemcpyDeviceToDevice, w->stream));
-		TRACE("integrate");
-		if (hasJoints && !exactLarge && !sortInIntegrate) LAUNCH(w, k_joints_sort, gJ, 64, d);
-		// (the warm start body by body in one launch - k_large_warm - where the sweep would be a launch per colour: k_large_init
-		// leaves the deltas for it)
-		const bool bodyWarm = w->bodyWarm && w->sweepEnd && !exactLarge && !w->debugTrace && !useSweep && sp.warmStarting && nColors <= MAX_COLORS;
-		LAUNCH(w, k_large_init, gC, 256, d, sp, bodyWarm ? 1 : 0);
-		TRACE("init");
-		// colours that own no constraint (the partition keeps two colour ranges apart) are not launched
-		const uint64_t colorMask = exactLarge ? ~0ull : ((uint64_t)w->h_dstate->c.colorMaskLo | ((uint64_t)w->h_dstate->c.colorMaskHi << 32));
-		auto colorUsed = [&](int col) { return col >= 64 || ((colorMask >> col) & 1ull) != 0; };
-		// every launch of k_blocks_sweep tags its hand-over rows with an epoch of its own (15 bits: the rows are wiped twice per round)
-		auto sweep = [&](int mode) -> int
-		{
-			if ((w->dfEpoch >> 14) != w->dfWipedAt)
-			{
-				HIP_TRY(hipMemsetAsync(w->b_cutv.p, 0, w->b_cutv.cap * sizeof(float4), w->stream));
-				HIP_TRY(hipMemsetAsync(w->b_posv.p, 0, w->b_posv.cap * sizeof(float4), w->stream));
-				w->dfWipedAt = w->dfEpoch >> 14;
-			}
-			if (c.blkLanes == 512) LAUNCH(w, k_blocks_sweep<512>, c.nBlocks, 512, d, sp, mode, w->gridBar.p, w->dfEpoch);
-			else if (c.blkLanes == 256) LAUNCH(w, k_blocks_sweep<256>, c.nBlocks, 256, d, sp, mode, w->gridBar.p, w->dfEpoch);
-			else if (c.blkLanes == BLOCK_LANES) LAUNCH(w, k_blocks_sweep<BLOCK_LANES>, c.nBlocks, BLOCK_LANES, d, sp, mode, w->gridBar.p, w->dfEpoch);
-			else return setError(B2HIP_ERR_INVALID, "block partition made for an unknown workgroup size");
-			w->dfEpoch += 1;
-			return 0;
-		};
-		// the hub sweeps: eight waves that fetch their chunks of hub constraints ahead of their turn (one wave on request)
-		auto hubSweepLaunch = [&](int mode, int useGuess, int behindWide = 0) -> int
-		{
-			if (w->hubWaves == 1) LAUNCH(w, k_large_hub<1>, 1, 64, d, mode, useGuess, behindWide);
-			else LAUNCH(w, k_large_hub<8>, 1, 512, d, mode, useGuess, behindWide);
-			return 0;
-		};
-		if (useSweep) w->sweepSteps += 1;
-		// ---- the end of every sweep in ONE single-workgroup launch (b2d_kernels_sweep_end.h): the tail colours - those this
-		// step's colour census (k_color_check, published with the island census) found small, from the highest colour down -
-		// the hub rows, the joint walk, the verdict of a position iteration. Which colours are "tail" changes nothing in the
-		// result (k_sweep_end does k_large_velocity's / k_large_position's arithmetic row for row): a pure launch-count matter.
-		const bool useRest = useSweepEnd && restFirst < nColors;
-		int tailFirst = useRest ? restFirst : nColors;
-		if (useSweepEnd && w->sweepTail && !useRest && !useSweep && !c.needRecolor && !censusVoid && nColors <= MAX_COLORS)
-		{
-			long long sum = 0;
-			while (tailFirst > 0 && c.colorRows[tailFirst - 1] <= w->tailRowsMax && sum + c.colorRows[tailFirst - 1] <= 8ll * w->tailRowsMax)
-			{
-				sum += c.colorRows[tailFirst - 1];
-				tailFirst -= 1;
-			}
-		}
-		bool tailAny = false;
-		for (int col = tailFirst; col < nColors && !useRest; ++col) tailAny = tailAny || colorUsed(col);
-		// (every launch of k_large_rest tags its hand-over rows with an epoch of its own, like k_blocks_sweep)
-		auto restLaunch = [&](int mode) -> int
-		{
-			if (!useRest) return 0;
-			if ((w->dfEpoch >> 14) != w->dfWipedAt)
-			{
-				HIP_TRY(hipMemsetAsync(w->b_cutv.p, 0, w->b_cutv.cap * sizeof(float4), w->stream));
-				HIP_TRY(hipMemsetAsync(w->b_posv.p, 0, w->b_posv.cap * sizeof(float4), w->stream));
-				w->dfWipedAt = w->dfEpoch >> 14;
-			}
-			long long rows = 0;
-			for (int col = restFirst; col < nColors && col < MAX_COLORS; ++col) rows += c.colorRows[col];
-			// (the census is this step's before k_color_small handed out its colours - at most COLOR_SMALL_MAX rows more)
-			int gR = (int)((rows + COLOR_SMALL_MAX + 255) / 256);
-			// (the workgroups wait for one another: no more of them than are resident together - the rest walk in strides)
-			if (w->restMaxWG > 0) gR = std::min(gR, w->restMaxWG);
-			if (mode == 0) LAUNCH(w, k_large_rest<0>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
-			else if (mode == 1) LAUNCH(w, k_large_rest<1>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
-			else LAUNCH(w, k_large_rest<2>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
-			w->dfEpoch += 1;
-			return 0;
-		};
-		w->lastTailFirst = tailFirst;
-		w->lastSweepLaunches = 0;
-		const int bigEnd = useSweep ? 0 : tailFirst; // colours [0, bigEnd) are launches of their own
-		// The hub rows the one fixed point cannot take are swept lane after lane inside k_sweep_end - a handful on the Tumbler
-		// (boxes in the corners). An island that kept many of them in the LAST step (several hubs, constraints swept in order for
-		// lack of a home block; the census still carries that step's counts) gets k_large_hub's eight prefetching waves for
-		// them: k_sweep_end up to the fixed point, k_large_hub, k_sweep_end for what follows the hub rows. (Either way a valid
-		// sweep; which one is decided from counters a snapshot carries, so a loaded world decides alike.)
-		const bool leftoverApart = useSweepEnd && hasHubs && d.hubWide && c.nHubRows - c.nHubWide > SE_LEFT_INLINE_MAX;
-		auto sweepEndOne = [&](int mode, int tf, int te, int what) -> int
-		{
-			if (mode == 0) LAUNCH(w, k_sweep_end<0>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
-			else if (mode == 1) LAUNCH(w, k_sweep_end<1>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
-			else LAUNCH(w, k_sweep_end<2>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
-			w->lastSweepLaunches += 1;
-			return 0;
-		};
-		// ---- k_large_rest and k_sweep_end of one sweep as ONE launch (k_rest_hub, round 6): the rest rows in gF workgroups of
-		// 512 lanes, the hub rows / joints / verdict in one more that waits for what it needs of them as tagged rows. All
-		// workgroups must be resident together (restHubMaxWG: the occupancy query at world creation).
-		const bool fuseHub = useRest && w->restHub && (hasHubs || hasJoints) && !leftoverApart && w->restHubMaxWG > 1;
-		auto restHubLaunch = [&](int mode, int what) -> int
-		{
-			if ((w->dfEpoch >> 14) != w->dfWipedAt)
-			{
-				HIP_TRY(hipMemsetAsync(w->b_cutv.p, 0, w->b_cutv.cap * sizeof(float4), w->stream));
-				HIP_TRY(hipMemsetAsync(w->b_posv.p, 0, w->b_posv.cap * sizeof(float4), w->stream));
-				w->dfWipedAt = w->dfEpoch >> 14;
-			}
-			long long rows = 0;
-			for (int col = restFirst; col < nColors && col < MAX_COLORS; ++col) rows += c.colorRows[col];
-			// (the census is this step's before k_color_small handed out its colours - at most COLOR_SMALL_MAX rows more; a grid
-			// that does not hold every row walks them in strides)
-			int gF = (int)((rows + COLOR_SMALL_MAX + SWEEP_END_LANES - 1) / SWEEP_END_LANES);
-			gF = std::max(1, std::min(gF, w->restHubMaxWG - 1));
-			if (mode == 2) w->restArrived += gF; // (the verdict of a position iteration waits for them: bar[5])
-			if (mode == 1) LAUNCH(w, k_rest_hub<1>, gF + 1, SWEEP_END_LANES, d, sp, restFirst, nColors, what, w->gridBar.p, w->dfEpoch, w->restArrived, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
-			else LAUNCH(w, k_rest_hub<2>, gF + 1, SWEEP_END_LANES, d, sp, restFirst, nColors, what, w->gridBar.p, w->dfEpoch, w->restArrived, (int*)nullptr);
-			w->dfEpoch += 1;
-			w->lastSweepLaunches += 1;
-			return 0;
-		};
-		bool noTail = false;
-		auto sweepEndLaunch = [&](int mode, int what) -> int
-		{
-			if (!what && (!tailAny || noTail)) return 0;
-			const int tf = (useSweep || useRest || noTail) ? 0 : tailFirst, te = (useSweep || useRest || noTail) ? 0 : nColors;
-			if (leftoverApart && (what & SE_HUB))
-			{
-				int rcl = sweepEndOne(mode, tf, te, (what & (SE_HUB | SE_GUESS)) | SE_HUB_WIDE_ONLY);
-				if (rcl) return rcl;
-				rcl = hubSweepLaunch(mode, (what & SE_GUESS) ? 1 : 0, 1);
-				if (rcl) return rcl;
-				const int rest = what & ~(SE_HUB | SE_GUESS);
-				return rest ? sweepEndOne(mode, 0, 0, rest) : 0;
-			}
-			return sweepEndOne(mode, tf, te, what);
-		};
-		if (sp.warmStarting)
-		{
-			if (useSweep) { rc = sweep(0); if (rc) return rc; }
-			else if (bodyWarm) LAUNCH(w, k_large_warm, gB, 256, d);
-			else
-			{
-				for (int col = 0; col < bigEnd; ++col)
-					if (colorUsed(col)) LAUNCH(w, k_large_velocity, gridOfColor(col), censusGrid ? kLanes : 256, d, col, 0);
-				rc = restLaunch(0);
-				if (rc) return rc;
-			}
-			if (useSweepEnd)
-			{
-				// (b2Island.cpp:256-268: the joints' InitVelocityConstraints follows the contacts' warm start; the first velocity
-				// iteration then begins with the joints)
-				const int what0 = (hasHubs ? SE_HUB : 0) | (hasJoints ? SE_JOINTS_INIT | (sp.velIters > 0 ? SE_JOINTS_VEL : 0) : 0);
-				// (after k_large_warm every colour has had its warm start: only what follows the colours is left)
-				noTail = bodyWarm; // (after k_large_warm every colour has had its warm start)
-				rc = sweepEndLaunch(0, what0);
-				noTail = false;
-				if (rc) return rc;
-			}
-			else if (hasHubs) { rc = hubSweepLaunch(0, 0); if (rc) return rc; }
-		}
-		TRACE("warmstart");
-		if (hasJoints && !(useSweepEnd && sp.warmStarting)) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 0);
-		for (int it = 0; it < sp.velIters; ++it)
-		{
-			// (with k_sweep_end the joint walk of iteration it is the last act of the sweep before it)
-			if (hasJoints && !(useSweepEnd && (it > 0 || sp.warmStarting))) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 1);
-			if (useSweep) { rc = sweep(1); if (rc) return rc; }
-			else
-			for (int col = 0; col < bigEnd; ++col)
-			{
-				if (!colorUsed(col)) continue;
-				if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 1; }
-				LAUNCH(w, k_large_velocity, gridOfColor(col), censusGrid ? kLanes : 256, d, col, 1);
-				if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; }
-				if (w->debugTrace) TRACE(("vel" + std::to_string(it) + "_c" + std::to_string(col)).c_str());
-			}
-			const int what1 = (hasHubs ? SE_HUB | (it > 0 ? SE_GUESS : 0) : 0) | (hasJoints && it + 1 < sp.velIters ? SE_JOINTS_VEL : 0);
-			if (fuseHub && !useSweep) { rc = restHubLaunch(1, what1); if (rc) return rc; }
-			else
-			{
-				if (!useSweep) { rc = restLaunch(1); if (rc) return rc; }
-				if (useSweepEnd)
-				{
-					rc = sweepEndLaunch(1, what1);
-					if (rc) return rc;
-				}
-				else if (hasHubs) { rc = hubSweepLaunch(1, it > 0 ? 1 : 0); if (rc) return rc; }
-			}
-		}
-		// (one launch for the three: k_large_after_velocity; apart where a trace wants to see each)
-		const bool afterFused = !w->debugTrace && sp.posIters > 0;
-		if (afterFused) LAUNCH(w, k_large_after_velocity, gridFor(std::max(nLContacts, nLBodies)), 256, d, sp);
-		else
-		{
-			LAUNCH(w, k_large_store_impulses, gC, 256, d);
-			TRACE("store_impulses");
-			LAUNCH(w, k_large_integrate_positions, gB, 256, d, sp);
-			TRACE("integrate_positions");
-		}
-		for (int it = 0; it < sp.posIters; ++it)
-		{
-			if ((!useSweepEnd || it == 0) && !(afterFused && it == 0)) LAUNCH(w, k_large_pos_begin, gridFor(nLIslands), 256, d);
-			if (useSweep) { rc = sweep(2); if (rc) return rc; }
-			else
-			for (int col = 0; col < bigEnd; ++col)
-			{
-				if (!colorUsed(col)) continue;
-				LAUNCH(w, k_large_position, gridOfColor(col), censusGrid ? kLanes : 256, d, col);
-				if (w->debugTrace) TRACE(("pos" + std::to_string(it) + "_c" + std::to_string(col)).c_str());
-			}
-			const int what2 = (hasHubs ? SE_HUB | (it > 0 ? SE_GUESS : 0) : 0) | (hasJoints ? SE_JOINTS_POS : 0) | SE_POS_END | (it + 1 < sp.posIters ? SE_POS_BEGIN : 0);
-			if (fuseHub && !useSweep && w->restHub > 1) { rc = restHubLaunch(2, what2); if (rc) return rc; continue; }
-			if (!useSweep) { rc = restLaunch(2); if (rc) return rc; }
-			if (useSweepEnd)
-			{
-				rc = sweepEndLaunch(2, what2);
-				if (rc) return rc;
-			}
-			else
-			{
-				if (hasHubs) { rc = hubSweepLaunch(2, it > 0 ? 1 : 0); if (rc) return rc; }
-				if (hasJoints) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 2);
-				LAUNCH(w, k_large_pos_end, 1, 256, d);
-			}
-		}
-		}
-		LAUNCH(w, k_large_finalize, gB, 256, d, sp);
-		TRACE("finalize");
-		LAUNCH(w, k_large_sleep, gB, 256, d, sp);
 		return 0;
-		};
-		rc = runLarge(false);
-		if (rc) return rc;
-		if (w->kernelTiming == 5 && w->ktKind == 8) { w->familyLaunches = (int)(w->launchCount - w->familyLaunchesAtStart); rc = ktRecord(w); if (rc) return rc; }
-		if (w->recoverOn && waitsBetweenWorkgroups)
+	}
+	s.sideStream = !s.exactLarge && s.c.nLIslands > 0 && !w->debugTrace && !w->kernelTimingLaunches && !w->noSideStream;
+	if (!s.sideStream) return launchSmallIslands(w, s, w->stream);
+	// fork here (the side stream needs the island build, nothing of the large-island solver); launches later.
+	// With the census polled the host has SEEN the island build finish (the publication is its last act): the side
+	// stream needs no event to wait for - an event record is a packet of its own on the main stream, ~6 us between
+	// the colouring and the solver
+	if (!s.poll) HIP_TRY(hipEventRecord(w->evFork, w->stream));
+	s.smallDeferred = true;
+	stampPhase(w, 5);
+	stampPhase(w, 6);
+	return 0;
+}
+
+static int launchDeferredSmallIslands(b2hip_world* w, SolveStep& s)
+{
+	if (!s.smallDeferred) return 0;
+	s.smallDeferred = false;
+	return launchSmallIslands(w, s, w->stream2);
+}
+
+// What the large-island solver runs over: the census's large islands, or in exact-order mode every island, with the
+// dependency levels of the reference's own constraint order as colours.
+static int sizeLargeIslands(b2hip_world* w, SolveStep& s)
+{
+	DW& d = w->dw;
+	const Counters& c = s.c;
+	s.nLIslands = c.nLIslands;
+	s.nLBodies = c.nLBodies;
+	s.nLContacts = c.nLContacts;
+	if (!s.exactLarge || c.nSIslands == 0) return 0;
+	LAUNCH(w, k_exact_begin, gridFor(c.nSContacts + 1), 256, d);
+	LAUNCH(w, k_exact_convert, gridFor(std::max(c.nSContacts, c.nSBodies)), 256, d);
+	if (int rc = readState(w)) return rc;
+	s.nColors = w->h_dstate->c.nColors;
+	s.nLIslands = c.nSIslands;
+	s.nLBodies = c.nSBodies;
+	s.nLContacts = c.nSContacts;
+	return 0;
+}
+
+// The solver of the large islands: k_solve_blocks (bodies in LDS, one workgroup per block of the partition) whenever the
+// partition fits; k_blocks_sweep (one launch per sweep over the same blocks) for islands that need joint walks / hub
+// sweeps in between; else a launch per colour.
+static void chooseLargeSolver(b2hip_world* w, SolveStep& s)
+{
+	const StepParams& sp = w->sp;
+	const Counters& c = s.c;
+	const bool partitionFits = s.blockShape && c.nBlocks > 0 && c.nOrphanRows == 0 && c.blkMaxRows <= c.blkLanes && c.blkMaxBodies <= c.blkLanes;
+	s.useBlocks = !s.exactLarge && s.plainIslands && !s.hasHubs && !w->debugTrace && !w->kernelTimingLaunches && partitionFits &&
+		c.nBlocks <= w->blocksMaxWG && (sp.velIters + 2) * (MAX_COLORS + 1) < 65536 && (sp.posIters + 1) * (MAX_COLORS + 1) < 65536;
+	const int sweepMaxWG = c.blkLanes == 512 ? w->sweepMaxWG[1] : (c.blkLanes == BLOCK_LANES ? w->sweepMaxWG[2] : w->sweepMaxWG[0]);
+	s.useSweep = !s.useBlocks && !s.exactLarge && partitionFits && !s.plainIslands && !w->debugTrace && !w->kernelTimingLaunches &&
+		c.nBlocks <= sweepMaxWG;
+	w->dw.blockSort = (s.useBlocks || s.useSweep) ? 1 : 0;
+}
+
+// The grid-wide colouring rounds (k_color_claim / k_color_resolve) until every constraint has a colour: `batch` rounds
+// before the first read-back, eight between the later ones.
+static int colorRoundsUntilDone(b2hip_world* w, SolveStep& s, int uncolored, int batch)
+{
+	DW& d = w->dw;
+	const int gC = gridFor(std::max(s.nLContacts, 1));
+	for (; uncolored > 0; batch = 8)
+	{
+		for (int r = 0; r < batch; ++r)
 		{
-			// did every wait come to its end? (the overflow word, published by one lane behind the solver; polled)
-			w->solverSeq = (w->solverSeq + 1) & 0x7fff;
-			LAUNCH(w, k_solver_status, 1, 64, d, w->d_solverWord, w->solverSeq);
-			rc = pollPublished(w, (volatile const int*)&w->h_solverWord[1], w->solverSeq, "solver status");
-			if (rc) return rc;
-			const int flags = w->h_solverWord[0];
-			// (a resident solver read the colours on the device: were they complete?)
-			const bool colorsBad = colorsOnDevice && ((flags & 4) != 0 || w->h_solverWord[2] != 0);
-			if (colorsOnDevice) w->colorSmallPending = false; // (looked at here)
-			if ((flags & 64) || colorsBad)
-			{
-				if (w->tracePartition || getenv("B2HIP_TRACE_RECOVERY")) fprintf(stderr, "[b2hip] a wait between workgroups of the large-island solver timed out (overflow 0x%x): saved state back, the solve once more launch by launch\n", flags);
-				LAUNCH(w, k_solver_snapshot, gridFor(std::max(nLBodies, nLContacts)), 256, d, 1);
-				LAUNCH(w, k_solver_recover_reset, gridFor(d.nBodies), 256, d, w->gridBar.p);
-				w->restArrived = 0;
-				rc = readState(w);
-				if (rc) return rc;
-				if (colorsBad)
-				{
-					if (getenv("B2HIP_TRACE_RECOVERY")) fprintf(stderr, "[b2hip] the resident solver ran on an incomplete colouring (overflow 0x%x, %d without a colour): colouring finished, the solve once more\n", flags, w->h_solverWord[2]);
-					// finish the colouring first: the grid-wide rounds over what k_color_small left open
-					int uncolored = w->h_dstate->c.nUncolored;
-					while (uncolored > 0)
-					{
-						for (int r = 0; r < 8; ++r)
-						{
-							LAUNCH(w, k_color_claim, gC, 256, d);
-							LAUNCH(w, k_color_resolve, gC, 256, d);
-						}
-						rc = readState(w);
-						if (rc) return rc;
-						uncolored = w->h_dstate->c.nUncolored;
-					}
-					if (w->h_dstate->c.overflow & 4) colorSpill = true;
-					censusVoid = true;
-					w->colorRecoveries += 1;
-				}
-				nColors = w->h_dstate->c.nColors;
-				if (nColors > HUB_COLOR) nColors = HUB_COLOR;
-				c.nColors = nColors;
-				memcpy(c.colorRows, w->h_dstate->c.colorRows, sizeof(c.colorRows));
-				if (flags & 64) w->solverRecoveries += 1;
-				rc = runLarge(true);
-				if (rc) return rc;
-			}
+			LAUNCH(w, k_color_claim, gC, 256, d);
+			LAUNCH(w, k_color_resolve, gC, 256, d);
 		}
-		TRACE("sleep");
-		if (sideStream) HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0));
-		stampPhase(w, 8);
+		if (int rc = readState(w)) return rc;
+		uncolored = w->h_dstate->c.nUncolored;
+		s.nColors = w->h_dstate->c.nColors;
+		if (w->h_dstate->c.overflow & 4) { if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "more than 64 constraint colours on one body"); s.colorSpill = true; }
+	}
+	return 0;
+}
+
+// Colours for the constraints of the large islands that have none (or all of them afresh).
+static int colorLargeIslands(b2hip_world* w, SolveStep& s)
+{
+	DW& d = w->dw;
+	Counters& c = s.c;
+	if (s.exactLarge || !(c.needRecolor || c.nUncolored > 0 || c.nCompact > 0)) return 0;
+	bool roundsToo = c.needRecolor || c.nUncolored > COLOR_SMALL_MAX; // the grid-wide rounds run (asked for by the census, or to finish what k_color_small left)
+	if (!roundsToo)
+	{
+		// the usual case (a few new contacts on a settled island, a colour class to compact): one workgroup colours them;
+		// k_solve_blocks reads the colour count from the device, the launch-per-colour path needs it: published by the
+		// kernel and polled - a copy + synchronise otherwise, B2HIP_NO_CENSUS_POLL=1
+		const bool pubColors = s.poll && !s.useBlocks;
+		if (!s.colorSmallQueued)
+		{
+			if (pubColors) w->pubSeq2 = (w->pubSeq2 + 1) & 0x3fffffff;
+			LAUNCH(w, k_color_small, 1, 1024, d, 0, 0, pubColors ? w->d_pub2 : (DState*)nullptr, w->pubSeq2); // (else: it went out behind the census)
+		}
+		if (s.useBlocks)
+		{
+			s.colorsOnDevice = true;
+			w->colorSmallPending = true;
+			return 0;
+		}
+		int rc;
+		if ((s.colorSmallQueued && s.colorAheadPublished) || (!s.colorSmallQueued && pubColors))
+		{
+			rc = awaitColors(w);
+			if (rc == 0) c.nColors = w->h_dstate->c.nColors;
+			if (rc == 0) memcpy(c.colorRows, w->h_dstate->c.colorRows, sizeof(c.colorRows));
+		}
+		else rc = readState(w);
+		if (rc) return rc;
+		s.nColors = w->h_dstate->c.nColors;
+		// (round 6: neither ends the step any more. A constraint without a free colour on its two bodies is swept in order
+		// with the hub rows - k_hub_flag; rounds that did not converge are finished by the grid-wide rounds below)
+		if (w->h_dstate->c.overflow & 4) { if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "more than 64 constraint colours on one body"); s.colorSpill = true; }
+		if (w->h_dstate->c.nUncolored == 0) return 0;
+		if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "incremental colouring did not converge");
+		c.nUncolored = w->h_dstate->c.nUncolored;
+		w->colorRecoveries += 1;
+		if (w->traceRecovery) fprintf(stderr, "[b2hip] k_color_small left %d constraints without a colour: the grid-wide rounds finish\n", c.nUncolored);
+	}
+	// a colour clash on some body -> colour the large islands from scratch; otherwise only the constraints that have no
+	// colour yet join the Jones-Plassmann rounds (existing masks stay)
+	s.censusVoid = true; // (thousands of constraints get their colours now: the colour census of this step is history)
+	int uncolored = c.nUncolored;
+	if (c.needRecolor)
+	{
+		LAUNCH(w, k_color_begin, gridFor(d.capContacts), 256, d);
+		uncolored = s.nLContacts; // upper bound (hub constraints excluded on the device); refreshed by the read-back
+	}
+	if (int rc = colorRoundsUntilDone(w, s, uncolored, c.needRecolor ? 8 : 2)) return rc;
+	if (w->freshColorsPending) { w->freshColors = s.nColors < 63 ? s.nColors : 63; w->freshColorsPending = false; }
+	return 0;
+}
+
+// The hand-over rows of k_solve_blocks / k_blocks_sweep / k_large_rest / k_rest_hub carry a 15-bit epoch of their launch
+// (w->dfEpoch): they are wiped whenever it comes round, so that a row nobody has written since cannot carry a matching tag.
+static int wipeHandoverRows(b2hip_world* w)
+{
+	if ((w->dfEpoch >> 14) == w->dfWipedAt) return 0;
+	HIP_TRY(hipMemsetAsync(w->b_cutv.p, 0, w->b_cutv.cap * sizeof(float4), w->stream));
+	HIP_TRY(hipMemsetAsync(w->b_posv.p, 0, w->b_posv.cap * sizeof(float4), w->stream));
+	w->dfWipedAt = w->dfEpoch >> 14;
+	return 0;
+}
+
+// ---- the row layout and the solver proper, as ONE unit that can run a second time in its SAFE form (round 6, VERDICT r05
+// item 5): b2World::Step has no failure path (b2World.cpp:1613-1710), and a wait between workgroups that times out - a
+// co-tenant on the device, a workgroup that was not resident - used to fail the step and leave a dead world. The unit
+// saves what the solver changes (k_solver_snapshot: rows of the large islands' bodies, impulses and flags of their
+// contacts, their joints) before its first solver launch; behind its last one a one-lane kernel publishes the overflow
+// word, the host looks at it (a poll of mapped memory: ~5 us with the next launch's latency - only where the unit used a
+// kernel whose workgroups wait for one another), and on a timed-out wait puts the saved state back and runs the unit
+// again on the plain path: rows by colour, a launch per colour, tail colours and hub rows in k_sweep_end's ONE workgroup -
+// nothing in it waits for another workgroup. Same colouring, same arithmetic, same order on every body: the bits the
+// fast path would have produced (tests/test_gpu_recovery.py).
+static int solveLargePass(b2hip_world* w, SolveStep& s, const bool safe)
+{
+	DW& d = w->dw;
+	const StepParams& sp = w->sp;
+	const Counters& c = s.c;
+	const int nColors = s.nColors, nLIslands = s.nLIslands, nLBodies = s.nLBodies, nLContacts = s.nLContacts;
+	const bool exactLarge = s.exactLarge, hasJoints = s.hasJoints;
+	int rc = 0;
+	if (safe)
+	{
+		s.useBlocks = s.useSweep = false;
+		s.colorsOnDevice = false;
+		d.blockSort = 0;
+	}
+	if (s.colorSpill) s.hasHubs = true; // (k_hub_flag lists the constraints that found no colour)
+	const bool hasHubs = s.hasHubs, useSweep = s.useSweep;
+	const int gB = gridFor(nLBodies), gC = gridFor(std::max(nLContacts, 1));
+	if (!d.blockSort) LAUNCH(w, k_color_scan, 1, 64, d); // (segments by colour: the block solvers sort their rows themselves)
+	// ---- the end of every sweep without a launch per colour (b2d_kernels_sweep_end.h). The REST colours - from the highest
+	// colour down while this step's colour census (k_color_check, published with the island census) keeps them below
+	// restRowsMax rows together - are swept by ONE launch of k_large_rest, as data flow per body; k_color_fill notes them
+	// on their bodies. Which colours are "rest" changes nothing in the result (the order on every body is the launches'):
+	// a launch-count matter. Not on a step that colours afresh: its census is void.
+	const bool useSweepEnd = w->sweepEnd && !exactLarge && !w->debugTrace;
+	int restFirst = 0x7fffffff; // (none)
+	if (useSweepEnd && w->restFlow && !safe && !d.blockSort && !c.needRecolor && !s.censusVoid && nColors > 0 && nColors < MAX_COLORS)
+	{
+		long long sum = 0;
+		int t = nColors;
+		while (t > 0 && sum + c.colorRows[t - 1] <= (long long)w->restRowsMax)
+		{
+			sum += c.colorRows[t - 1];
+			t -= 1;
+		}
+		if (nColors - t >= 2) restFirst = t;
+	}
+	w->lastRestFirst = restFirst < nColors ? restFirst : nColors;
+	// (the census is this step's before k_color_small handed out its colours - at most COLOR_SMALL_MAX rows more)
+	long long restRows = COLOR_SMALL_MAX;
+	for (int col = restFirst; col < nColors && col < MAX_COLORS; ++col) restRows += c.colorRows[col];
+	LAUNCH(w, k_color_fill, gC, 256, d, restFirst < MAX_COLORS ? restFirst : MAX_COLORS);
+	// (round 6: one single-workgroup launch sorts the hub group's segment of the row array in place - k_hub_build - where the
+	// last step's list was short enough for its keys to sit in LDS; the four launches below otherwise)
+	const bool hubBuildOne = hasHubs && !w->noHubBuild && w->last.nHubRows <= HUB_BUILD_LDS;
+	if (hubBuildOne)
+	{
+		LAUNCH(w, k_hub_build, 1, 1024, d, d.hubWide ? 1 : 0, (!w->noHubOrder && (d.hubWide || w->hubOrderAll)) ? 1 : 0, d.blockSort ? 1 : 0);
+		w->hubSteps += 1;
+	}
+	else if (hasHubs)
+	{
+		// the hub constraints in contact-index order (deterministic whatever the atomics of k_color_fill did)
+		LAUNCH(w, k_hub_flag, gridFor(d.capContacts), 256, d);
+		deviceExclusiveScan<int>(w->stream, d.keepFlag, d.keepScan, d.scanTmp, w->scanCtx, &d.st->c.nContacts, d.capContacts);
+		LAUNCH(w, k_hub_fill, gridFor(d.capContacts), 256, d);
+		// (the hub meets its partners in the order of their highest colour: b2d_kernels_solve_large.h, k_hub_order)
+		if (!w->noHubOrder && (d.hubWide || w->hubOrderAll)) LAUNCH(w, k_hub_order, 1, 1024, d, d.hubWide ? 0 : 1);
+		w->hubSteps += 1;
+	}
+	stampPhase(w, 7);
+	const int gK = gridFor(std::max(nLContacts / std::max(nColors, 1), 1) * 2);
+	// A colour launch is a chain of dependent loads per lane (~4.5 us whatever it holds): a lane that makes a second trip
+	// of the grid-stride loop pays the chain twice - the Tumbler's five biggest colours (41 000 - 42 000 rows against a grid
+	// of 39 000 lanes sized from the MEAN colour) took 8 us instead of 6. Sized per colour from this step's census now
+	// (+ what k_color_small may still add), in workgroups of 256 lanes so that the rows spread over all CUs.
+	const bool censusGrid = !exactLarge && nColors > 0 && nColors <= MAX_COLORS && !c.needRecolor && !s.censusVoid;
+	auto gridOfColor = [&](int col) -> int
+	{
+		if (!censusGrid || col < 0 || col >= MAX_COLORS) return gK;
+		return gridFor((size_t)c.colorRows[col] + 512, 256, 1 << 16);
+	};
+	const int gJ = gridFor(std::max(nLIslands, 1), 64, 1 << 16);
+	s.waitsBetweenWorkgroups = s.useBlocks || useSweep || (useSweepEnd && restFirst < nColors);
+	if (!safe && w->recoverOn && s.waitsBetweenWorkgroups) LAUNCH(w, k_solver_snapshot, gridFor(std::max(nLBodies, nLContacts)), 256, d, 0);
+	if (s.useBlocks)
+	{
+		// one resident grid for the whole sweep structure; colour boundaries are barriers inside the blocks, the cut rows
+		// hand-overs between them (b2d_kernels_solve_blocks.h)
+		if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 4; }
+		if ((rc = wipeHandoverRows(w))) return rc;
+		if (c.blkLanes == 512) LAUNCH(w, k_solve_blocks<512>, c.nBlocks, 512, d, sp, w->gridBar.p, w->dfEpoch);
+		else if (c.blkLanes == 256) LAUNCH(w, k_solve_blocks<256>, c.nBlocks, 256, d, sp, w->gridBar.p, w->dfEpoch);
+		else if (c.blkLanes == BLOCK_LANES) LAUNCH(w, k_solve_blocks<BLOCK_LANES>, c.nBlocks, BLOCK_LANES, d, sp, w->gridBar.p, w->dfEpoch);
+		else return setError(B2HIP_ERR_INVALID, "block partition made for an unknown workgroup size");
+		w->dfEpoch += 1;
+		w->blockSteps += 1;
+		w->blocksThisStep = true;
+		if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; }
+		if ((rc = launchDeferredSmallIslands(w, s))) return rc;
 	}
 	else
 	{
-		stampPhase(w, 7);
-		stampPhase(w, 8);
+	if ((rc = launchDeferredSmallIslands(w, s))) return rc;
+	TRACE("before_integrate");
+	if (w->debugTrace)
+	{
+		const size_t nb = w->bodies.size();
+		(void)w->dbgPreVel.ensure(nb, w->stream); (void)w->dbgVel.ensure(nb, w->stream); (void)w->dbgLi.ensure(nb + 64, w->stream);
+		HIP_TRY(hipMemcpyAsync(w->dbgPreVel.p, w->b_vel.p, nb * 16, hipMemcpyDeviceToDevice, w->stream));
+		HIP_TRY(hipMemcpyAsync(w->dbgLi.p, w->li_bodies.p, nb * 4, hipMemcpyDeviceToDevice, w->stream));
+		HIP_TRY(hipMemcpyAsync(w->dbgLi.p + nb, &w->d_state.p->c, 64 * 4 > sizeof(Counters) ? sizeof(Counters) : 64 * 4, hipMemcpyDeviceToDevice, w->stream));
 	}
+	// (timing mode 5: ONE event pair around the whole large-island solver family of the launch-per-colour path - integrate,
+	// constraint set-up, every sweep, impulses stored, positions, write-back and sleep)
+	if (w->kernelTiming == 5 && !safe) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 8; w->familyLaunchesAtStart = w->launchCount; }
+	const bool sortInIntegrate = hasJoints && !exactLarge && !w->debugTrace;
+	LAUNCH(w, k_large_integrate, gB, 256, d, sp, sortInIntegrate ? 1 : 0);
+	if (w->debugTrace) HIP_TRY(hipMemcpyAsync(w->dbgVel.p, w->b_vel.p, w->bodies.size() * 16, hipMemcpyDeviceToDevice, w->stream));
+	TRACE("integrate");
+	if (hasJoints && !exactLarge && !sortInIntegrate) LAUNCH(w, k_joints_sort, gJ, 64, d);
+	// (the warm start body by body in one launch - k_large_warm - where the sweep would be a launch per colour: k_large_init
+	// leaves the deltas for it)
+	const bool bodyWarm = w->bodyWarm && w->sweepEnd && !exactLarge && !w->debugTrace && !useSweep && sp.warmStarting && nColors <= MAX_COLORS;
+	LAUNCH(w, k_large_init, gC, 256, d, sp, bodyWarm ? 1 : 0);
+	TRACE("init");
+	// colours that own no constraint (the partition keeps two colour ranges apart) are not launched
+	const uint64_t colorMask = exactLarge ? ~0ull : ((uint64_t)w->h_dstate->c.colorMaskLo | ((uint64_t)w->h_dstate->c.colorMaskHi << 32));
+	auto colorUsed = [&](int col) { return col >= 64 || ((colorMask >> col) & 1ull) != 0; };
+	// every launch of k_blocks_sweep tags its hand-over rows with an epoch of its own
+	auto sweep = [&](int mode) -> int
+	{
+		if (int rcw = wipeHandoverRows(w)) return rcw;
+		if (c.blkLanes == 512) LAUNCH(w, k_blocks_sweep<512>, c.nBlocks, 512, d, sp, mode, w->gridBar.p, w->dfEpoch);
+		else if (c.blkLanes == 256) LAUNCH(w, k_blocks_sweep<256>, c.nBlocks, 256, d, sp, mode, w->gridBar.p, w->dfEpoch);
+		else if (c.blkLanes == BLOCK_LANES) LAUNCH(w, k_blocks_sweep<BLOCK_LANES>, c.nBlocks, BLOCK_LANES, d, sp, mode, w->gridBar.p, w->dfEpoch);
+		else return setError(B2HIP_ERR_INVALID, "block partition made for an unknown workgroup size");
+		w->dfEpoch += 1;
+		return 0;
+	};
+	// the hub sweeps: eight waves that fetch their chunks of hub constraints ahead of their turn (one wave on request)
+	auto hubSweepLaunch = [&](int mode, int useGuess, int behindWide = 0) -> int
+	{
+		if (w->hubWaves == 1) LAUNCH(w, k_large_hub<1>, 1, 64, d, mode, useGuess, behindWide);
+		else LAUNCH(w, k_large_hub<8>, 1, 512, d, mode, useGuess, behindWide);
+		return 0;
+	};
+	if (useSweep) w->sweepSteps += 1;
+	// ---- the end of every sweep in ONE single-workgroup launch (b2d_kernels_sweep_end.h): the tail colours - those this
+	// step's colour census (k_color_check, published with the island census) found small, from the highest colour down -
+	// the hub rows, the joint walk, the verdict of a position iteration. Which colours are "tail" changes nothing in the
+	// result (k_sweep_end does k_large_velocity's / k_large_position's arithmetic row for row): a pure launch-count matter.
+	const bool useRest = useSweepEnd && restFirst < nColors;
+	int tailFirst = useRest ? restFirst : nColors;
+	if (useSweepEnd && w->sweepTail && !useRest && !useSweep && !c.needRecolor && !s.censusVoid && nColors <= MAX_COLORS)
+	{
+		long long sum = 0;
+		while (tailFirst > 0 && c.colorRows[tailFirst - 1] <= w->tailRowsMax && sum + c.colorRows[tailFirst - 1] <= 8ll * w->tailRowsMax)
+		{
+			sum += c.colorRows[tailFirst - 1];
+			tailFirst -= 1;
+		}
+	}
+	bool tailAny = false;
+	for (int col = tailFirst; col < nColors && !useRest; ++col) tailAny = tailAny || colorUsed(col);
+	// (every launch of k_large_rest tags its hand-over rows with an epoch of its own, like k_blocks_sweep)
+	auto restLaunch = [&](int mode) -> int
+	{
+		if (!useRest) return 0;
+		if (int rcw = wipeHandoverRows(w)) return rcw;
+		int gR = (int)((restRows + 255) / 256);
+		// (the workgroups wait for one another: no more of them than are resident together - the rest walk in strides)
+		if (w->restMaxWG > 0) gR = std::min(gR, w->restMaxWG);
+		if (mode == 0) LAUNCH(w, k_large_rest<0>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
+		else if (mode == 1) LAUNCH(w, k_large_rest<1>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
+		else LAUNCH(w, k_large_rest<2>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
+		w->dfEpoch += 1;
+		return 0;
+	};
+	w->lastTailFirst = tailFirst;
+	w->lastSweepLaunches = 0;
+	const int bigEnd = useSweep ? 0 : tailFirst; // colours [0, bigEnd) are launches of their own
+	// The hub rows the one fixed point cannot take are swept lane after lane inside k_sweep_end - a handful on the Tumbler
+	// (boxes in the corners). An island that kept many of them in the LAST step (several hubs, constraints swept in order for
+	// lack of a home block; the census still carries that step's counts) gets k_large_hub's eight prefetching waves for
+	// them: k_sweep_end up to the fixed point, k_large_hub, k_sweep_end for what follows the hub rows. (Either way a valid
+	// sweep; which one is decided from counters a snapshot carries, so a loaded world decides alike.)
+	const bool leftoverApart = useSweepEnd && hasHubs && d.hubWide && c.nHubRows - c.nHubWide > SE_LEFT_INLINE_MAX;
+	auto sweepEndOne = [&](int mode, int tf, int te, int what) -> int
+	{
+		if (mode == 0) LAUNCH(w, k_sweep_end<0>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
+		else if (mode == 1) LAUNCH(w, k_sweep_end<1>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
+		else LAUNCH(w, k_sweep_end<2>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
+		w->lastSweepLaunches += 1;
+		return 0;
+	};
+	// ---- k_large_rest and k_sweep_end of one sweep as ONE launch (k_rest_hub, round 6): the rest rows in gF workgroups of
+	// 512 lanes, the hub rows / joints / verdict in one more that waits for what it needs of them as tagged rows. All
+	// workgroups must be resident together (restHubMaxWG: the occupancy query at world creation).
+	const bool fuseHub = useRest && w->restHub && (hasHubs || hasJoints) && !leftoverApart && w->restHubMaxWG > 1;
+	auto restHubLaunch = [&](int mode, int what) -> int
+	{
+		if (int rcw = wipeHandoverRows(w)) return rcw;
+		// (a grid that does not hold every row walks them in strides)
+		int gF = (int)((restRows + SWEEP_END_LANES - 1) / SWEEP_END_LANES);
+		gF = std::max(1, std::min(gF, w->restHubMaxWG - 1));
+		if (mode == 2) w->restArrived += gF; // (the verdict of a position iteration waits for them: bar[5])
+		if (mode == 1) LAUNCH(w, k_rest_hub<1>, gF + 1, SWEEP_END_LANES, d, sp, restFirst, nColors, what, w->gridBar.p, w->dfEpoch, w->restArrived, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
+		else LAUNCH(w, k_rest_hub<2>, gF + 1, SWEEP_END_LANES, d, sp, restFirst, nColors, what, w->gridBar.p, w->dfEpoch, w->restArrived, (int*)nullptr);
+		w->dfEpoch += 1;
+		w->lastSweepLaunches += 1;
+		return 0;
+	};
+	bool noTail = false;
+	auto sweepEndLaunch = [&](int mode, int what) -> int
+	{
+		if (!what && (!tailAny || noTail)) return 0;
+		const int tf = (useSweep || useRest || noTail) ? 0 : tailFirst, te = (useSweep || useRest || noTail) ? 0 : nColors;
+		if (leftoverApart && (what & SE_HUB))
+		{
+			int rcl = sweepEndOne(mode, tf, te, (what & (SE_HUB | SE_GUESS)) | SE_HUB_WIDE_ONLY);
+			if (rcl) return rcl;
+			rcl = hubSweepLaunch(mode, (what & SE_GUESS) ? 1 : 0, 1);
+			if (rcl) return rcl;
+			const int rest = what & ~(SE_HUB | SE_GUESS);
+			return rest ? sweepEndOne(mode, 0, 0, rest) : 0;
+		}
+		return sweepEndOne(mode, tf, te, what);
+	};
+	if (sp.warmStarting)
+	{
+		if (useSweep) { rc = sweep(0); if (rc) return rc; }
+		else if (bodyWarm) LAUNCH(w, k_large_warm, gB, 256, d);
+		else
+		{
+			for (int col = 0; col < bigEnd; ++col)
+				if (colorUsed(col)) LAUNCH(w, k_large_velocity, gridOfColor(col), 256, d, col, 0);
+			rc = restLaunch(0);
+			if (rc) return rc;
+		}
+		if (useSweepEnd)
+		{
+			// (b2Island.cpp:256-268: the joints' InitVelocityConstraints follows the contacts' warm start; the first velocity
+			// iteration then begins with the joints)
+			const int what0 = (hasHubs ? SE_HUB : 0) | (hasJoints ? SE_JOINTS_INIT | (sp.velIters > 0 ? SE_JOINTS_VEL : 0) : 0);
+			noTail = bodyWarm; // (after k_large_warm every colour has had its warm start: only what follows the colours is left)
+			rc = sweepEndLaunch(0, what0);
+			noTail = false;
+			if (rc) return rc;
+		}
+		else if (hasHubs) { rc = hubSweepLaunch(0, 0); if (rc) return rc; }
+	}
+	TRACE("warmstart");
+	if (hasJoints && !(useSweepEnd && sp.warmStarting)) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 0);
+	for (int it = 0; it < sp.velIters; ++it)
+	{
+		// (with k_sweep_end the joint walk of iteration it is the last act of the sweep before it)
+		if (hasJoints && !(useSweepEnd && (it > 0 || sp.warmStarting))) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 1);
+		if (useSweep) { rc = sweep(1); if (rc) return rc; }
+		else
+		for (int col = 0; col < bigEnd; ++col)
+		{
+			if (!colorUsed(col)) continue;
+			if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 1; }
+			LAUNCH(w, k_large_velocity, gridOfColor(col), 256, d, col, 1);
+			if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; }
+			if (w->debugTrace) TRACE(("vel" + std::to_string(it) + "_c" + std::to_string(col)).c_str());
+		}
+		const int what1 = (hasHubs ? SE_HUB | (it > 0 ? SE_GUESS : 0) : 0) | (hasJoints && it + 1 < sp.velIters ? SE_JOINTS_VEL : 0);
+		if (fuseHub && !useSweep) { rc = restHubLaunch(1, what1); if (rc) return rc; }
+		else
+		{
+			if (!useSweep) { rc = restLaunch(1); if (rc) return rc; }
+			if (useSweepEnd)
+			{
+				rc = sweepEndLaunch(1, what1);
+				if (rc) return rc;
+			}
+			else if (hasHubs) { rc = hubSweepLaunch(1, it > 0 ? 1 : 0); if (rc) return rc; }
+		}
+	}
+	// (one launch for the three: k_large_after_velocity; apart where a trace wants to see each)
+	const bool afterFused = !w->debugTrace && sp.posIters > 0;
+	if (afterFused) LAUNCH(w, k_large_after_velocity, gridFor(std::max(nLContacts, nLBodies)), 256, d, sp);
+	else
+	{
+		LAUNCH(w, k_large_store_impulses, gC, 256, d);
+		TRACE("store_impulses");
+		LAUNCH(w, k_large_integrate_positions, gB, 256, d, sp);
+		TRACE("integrate_positions");
+	}
+	for (int it = 0; it < sp.posIters; ++it)
+	{
+		if ((!useSweepEnd || it == 0) && !(afterFused && it == 0)) LAUNCH(w, k_large_pos_begin, gridFor(nLIslands), 256, d);
+		if (useSweep) { rc = sweep(2); if (rc) return rc; }
+		else
+		for (int col = 0; col < bigEnd; ++col)
+		{
+			if (!colorUsed(col)) continue;
+			LAUNCH(w, k_large_position, gridOfColor(col), 256, d, col);
+			if (w->debugTrace) TRACE(("pos" + std::to_string(it) + "_c" + std::to_string(col)).c_str());
+		}
+		const int what2 = (hasHubs ? SE_HUB | (it > 0 ? SE_GUESS : 0) : 0) | (hasJoints ? SE_JOINTS_POS : 0) | SE_POS_END | (it + 1 < sp.posIters ? SE_POS_BEGIN : 0);
+		if (fuseHub && !useSweep && w->restHub > 1) { rc = restHubLaunch(2, what2); if (rc) return rc; continue; }
+		if (!useSweep) { rc = restLaunch(2); if (rc) return rc; }
+		if (useSweepEnd)
+		{
+			rc = sweepEndLaunch(2, what2);
+			if (rc) return rc;
+		}
+		else
+		{
+			if (hasHubs) { rc = hubSweepLaunch(2, it > 0 ? 1 : 0); if (rc) return rc; }
+			if (hasJoints) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 2);
+			LAUNCH(w, k_large_pos_end, 1, 256, d);
+		}
+	}
+	}
+	LAUNCH(w, k_large_finalize, gB, 256, d, sp);
+	TRACE("finalize");
+	LAUNCH(w, k_large_sleep, gB, 256, d, sp);
+	return 0;
+}
+
+// Did every wait between workgroups come to its end? (the overflow word, published by one lane behind the solver; polled)
+// If not - or if k_solve_blocks ran on an incomplete colouring - the saved state goes back and the large islands are
+// solved once more, on the safe path.
+static int recoverLarge(b2hip_world* w, SolveStep& s)
+{
+	DW& d = w->dw;
+	w->solverSeq = (w->solverSeq + 1) & 0x7fff;
+	LAUNCH(w, k_solver_status, 1, 64, d, w->d_solverWord, w->solverSeq);
+	if (int rc = pollPublished(w, (volatile const int*)&w->h_solverWord[1], w->solverSeq, "solver status")) return rc;
+	const int flags = w->h_solverWord[0];
+	// (k_solve_blocks read the colours on the device: were they complete?)
+	const bool colorsBad = s.colorsOnDevice && ((flags & 4) != 0 || w->h_solverWord[2] != 0);
+	if (s.colorsOnDevice) w->colorSmallPending = false; // (looked at here)
+	if (!(flags & 64) && !colorsBad) return 0;
+	if (w->tracePartition || w->traceRecovery) fprintf(stderr, "[b2hip] a wait between workgroups of the large-island solver timed out (overflow 0x%x): saved state back, the solve once more launch by launch\n", flags);
+	LAUNCH(w, k_solver_snapshot, gridFor(std::max(s.nLBodies, s.nLContacts)), 256, d, 1);
+	LAUNCH(w, k_solver_recover_reset, gridFor(d.nBodies), 256, d, w->gridBar.p);
+	w->restArrived = 0;
+	if (int rc = readState(w)) return rc;
+	if (colorsBad)
+	{
+		if (w->traceRecovery) fprintf(stderr, "[b2hip] the resident solver ran on an incomplete colouring (overflow 0x%x, %d without a colour): colouring finished, the solve once more\n", flags, w->h_solverWord[2]);
+		// finish the colouring first: the grid-wide rounds over what k_color_small left open
+		if (int rc = colorRoundsUntilDone(w, s, w->h_dstate->c.nUncolored, 8)) return rc;
+		if (w->h_dstate->c.overflow & 4) s.colorSpill = true;
+		s.censusVoid = true;
+		w->colorRecoveries += 1;
+	}
+	s.nColors = std::min(w->h_dstate->c.nColors, (int)HUB_COLOR);
+	s.c.nColors = s.nColors;
+	memcpy(s.c.colorRows, w->h_dstate->c.colorRows, sizeof(s.c.colorRows));
+	if (flags & 64) w->solverRecoveries += 1;
+	return solveLargePass(w, s, true);
+}
+
+static int solveLargeIslands(b2hip_world* w, SolveStep& s)
+{
+	if (!s.exactLarge) s.nColors = s.c.nColors;
+	s.hasJoints = w->dw.nJoints > 0;
+	chooseLargeSolver(w, s);
+	if (int rc = colorLargeIslands(w, s)) return rc;
+	if (s.colorSpill) w->colorRecoveries += 1;
+	// (a constraint without a colour carries HUB_COLOR: the colours to launch end below it)
+	if (!s.exactLarge && s.nColors > HUB_COLOR) s.nColors = HUB_COLOR;
+	if (int rc = solveLargePass(w, s, false)) return rc;
+	if (w->kernelTiming == 5 && w->ktKind == 8)
+	{
+		w->familyLaunches = (int)(w->launchCount - w->familyLaunchesAtStart);
+		if (int rc = ktRecord(w)) return rc;
+	}
+	if (w->recoverOn && s.waitsBetweenWorkgroups)
+		if (int rc = recoverLarge(w, s)) return rc;
+	TRACE("sleep");
+	if (s.sideStream) HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0));
+	return 0;
+}
+
+static void recordSolveCounters(b2hip_world* w, const SolveStep& s)
+{
+	const Counters& c = s.c;
 	w->last.nSIslands = c.nSIslands;
 	w->last.nFreeIslands = c.nFreeIslands;
 	w->last.nSBodies = c.nSBodies;
 	w->last.nSContacts = c.nSContacts;
 	w->last.nChunks = c.nChunks;
-	w->last.nLIslands = nLIslands;
-	w->last.nLBodies = nLBodies;
-	w->last.nLContacts = nLContacts;
+	w->last.nLIslands = s.nLIslands;
+	w->last.nLBodies = s.nLBodies;
+	w->last.nLContacts = s.nLContacts;
 	w->last.nIslands = c.nIslands;
-	w->last.nColors = nColors;
+	w->last.nColors = s.nColors;
 	w->last.nTouching = c.nTouching;
 	w->last.nDestroy = c.nDestroy;
 	w->last.nBlocks = c.nBlocks;
 	w->last.nCutRows = c.nCutRows;
 	w->last.blkMaxRows = c.blkMaxRows;
 	w->last.partitions = c.partitions;
+}
+
+static int phaseSolve(b2hip_world* w)
+{
+	w->trace.clear();
+	w->blocksThisStep = false;
+	w->dw.serialOrphans = w->serialOrphansNext;
+	if (w->kernelTiming <= 1)
+	{
+		// (the event pairs of the solver kernels belong to this phase; those of k_collide / k_sync_fixtures / k_find_pairs_small -
+		// timing modes 2 to 4 - are taken in other phases of the step and cleared by b2hip_step_begin)
+		w->ktUsed = 0;
+		w->ktKind = 0;
+	}
+	SolveStep s;
+	s.poll = !w->noCensusPoll;
+	s.largeHint = w->largeHintSteps > 0;
+	s.exactLarge = w->forceLarge == 2;
+	int rc = buildIslands(w, s);
+	if (rc == 0) rc = awaitIslandCensus(w, s);
+	if (rc == 0) rc = largeIslandPolicy(w, s);
+	if (rc == 0) rc = repartition(w, s);
+	if (rc) return rc;
+	stampPhase(w, 4);
+	s.hasHubs = !s.exactLarge && (s.c.maxDegree > HUB_DEGREE || s.c.nSerialOrphans > 0);
+	rc = solveSmallIslands(w, s);
+	if (rc == 0) rc = sizeLargeIslands(w, s);
+	if (rc) return rc;
+	if (s.nLIslands > 0)
+	{
+		if ((rc = solveLargeIslands(w, s))) return rc;
+		stampPhase(w, 8);
+	}
+	else
+	{
+		stampPhase(w, 7);
+		stampPhase(w, 8);
+	}
+	recordSolveCounters(w, s);
 	return 0;
 }
 

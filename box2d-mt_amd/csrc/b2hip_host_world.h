@@ -92,13 +92,6 @@ struct HostFixture
 	bool noProxy;     // the body is inactive (b2Body::SetActive(false)): the fixture lives on without a broad-phase proxy
 };
 
-struct GraphSeg
-{
-	hipGraph_t graph = nullptr;
-	hipGraphExec_t exec = nullptr;
-	uint64_t sig = 0;
-};
-
 struct FreeUnit
 {
 	int leaf;
@@ -178,8 +171,7 @@ struct b2hip_world
 	DevArray<int> li_bodies, li_contacts, li_roots, li_color, colorCount, colorStart, colorCursor, li_sorted;
 	DevArray<uint32_t> bodyClaim, rootPen, rootSleepMin;
 	DevArray<uint64_t> bodyColorMask, bodyActive, bodyRest;
-	DevArray<float4> b_posv, dfInbox;
-	DevArray<int> dfRank;
+	DevArray<float4> b_posv;
 	DevArray<unsigned long long> evKey;
 	DevArray<int4> evInfo;
 	bool eventsOn = false;
@@ -247,7 +239,7 @@ struct b2hip_world
 	DevArray<float> stateOut;
 	DevArray<int> gridBar;       // grid barrier state of the persistent solver
 	int dfEpoch;
-	bool solverRows, solverLocal, solverMailbox, noSideStream, profileDetail;
+	bool noSideStream, profileDetail;
 	int collideStage = -1;       // B2HIP_COLLIDE_STAGE=0 / 1: never / always stage the shape records through LDS (default: by the record count)
 	int solidRoundsEnv = 0;      // B2HIP_SOLID_ROUNDS=1 / 2 / 4 / 8: the tile of the island build's passes over the contacts (x 256 contacts), else by the contact count
 	int collideSplitEnv = -1;    // B2HIP_COLLIDE_SPLIT=0 / 1: k_collide with the TOI-order replay inside / as a launch of its own (four waves per SIMD), else by the contact count
@@ -255,9 +247,6 @@ struct b2hip_world
 	int collideSortEnv = -1;     // B2HIP_COLLIDE_SORT=0 / 1: k_collide never / always sorts the contacts of a tile by shape-pair class in LDS
 	hipStream_t stream2 = nullptr; // small-island solver beside the large-island one
 	hipEvent_t evFork = nullptr, evJoin = nullptr;
-	int dfLanesForced, dfSleep, nCU; // k_solve_dataflow: workgroup size, poll back-off, co-resident workgroups
-	int persistMaxWG;            // co-resident workgroups of k_solve_persistent on this device (0 = do not use it)
-	int persistSteps;            // steps solved by the persistent kernel (diagnostics)
 	DevArray<int> consts; // [0] nBodies, [1] gridSize, [2] radix hist count, [3] sorted-pair count
 	DevArray<unsigned long long> filterPairs; // sorted body-pair keys of the joints created / destroyed since the last step
 	std::vector<int> nonStatic;       // the reference's m_nonStaticBodies: body ids in its order (island seed order)
@@ -299,7 +288,6 @@ struct b2hip_world
 	                             // workgroup ~4.5 us - the same chain of dependent loads a launch pays - so a colour of 8 000
 	                             // rows is 9 rounds = 40 us against 5.8 us as a launch of its own (tail colours up to 8 192 rows:
 	                             // 4.94 ms per step; none: 3.87; round 4's launches: 4.57)
-	int recolorSlack = 2;        // colour afresh when the colours in use exceed the last fresh colouring's by more than this (B2HIP_RECOLOR_SLACK; -1: every 64th step as in round 4)
 	int freshColors = 0;         // colours the last colouring from scratch of a partition-less world needed (0: none yet); in the snapshot's hints
 	bool freshColorsPending = false;
 	bool forceOnDevice = true;   // some body's force / torque row on the device may be non-zero (set by uploads, reset by a clearing read-back): the
@@ -312,9 +300,6 @@ struct b2hip_world
 	bool noHubBuild = false;     // B2HIP_NO_HUB_BUILD=1: the hub list by k_hub_flag + scan + k_hub_fill + k_hub_order (four launches) always
 	bool noHubOrder = false;     // B2HIP_NO_HUB_ORDER=1: the hub rows in contact order (round 5)
 	bool hubOrderAll = false;    // B2HIP_HUB_ORDER=1: ... ordered also where every hub row is swept lane after lane (B2HIP_HUB_WIDE=0 / B2HIP_HUB_SERIAL=1: comparison runs)
-	bool colorAheadOff = false;  // B2HIP_NO_COLOR_AHEAD=1: round 5's flow (the queued k_color_small returns where there is no partition, the colour count comes by copy)
-	bool noCensusGrid = false;   // B2HIP_NO_CENSUS_GRID=1: every colour launch sized from the mean colour (round 5)
-	int colorLanes = 256;        // lanes per workgroup of a colour launch (k_large_velocity / k_large_position; B2HIP_COLOR_LANES = 64 | 128 | 256)
 	bool recoverOn = true;       // a timed-out wait between workgroups of the large-island solver is recovered from (saved state back, the
 	                             // solve once more launch by launch; B2HIP_NO_RECOVER=1: the step fails as in round 5)
 	int* h_solverWord = nullptr; // mapped host memory: [0] the overflow word behind the solver, [1] the publication's number (k_solver_status)
@@ -340,6 +325,12 @@ struct b2hip_world
 	bool adoptPasses = false;    // the last step had orphan constraints (or made a partition): run k_block_adopt this step
 	bool traceLaunches = false;  // B2HIP_TRACE_LAUNCHES=1 (with B2HIP_DEBUG): every kernel's name before the stream is drained behind it
 	bool tracePartition = false; // B2HIP_TRACE_PARTITION=1: why a partition was made, on stderr
+	bool traceRecovery = false;  // B2HIP_TRACE_RECOVERY=1: every recovery, on stderr
+	bool toiWhy = false;         // B2HIP_TOI_WHY: why a parallel TOI path handed the phase to the serial loop, on stderr
+	bool handoverWhy = false;    // B2HIP_HANDOVER_WHY: the post mortem of a timed-out wait inside a block solver, on stderr
+	bool shardTrace = false;     // B2HIP_SHARD_TRACE=1: the size of every all-gather of a spatially sharded world (rank 0), on stderr
+	double stepDeadlineS = 300.0; // B2HIP_STEP_DEADLINE_S: a poll of the host gives up on a stream that stays busy this long
+	int pollDelayUs = 0;         // B2HIP_TEST_POLL_DELAY_US: the host comes late to its census poll (tests)
 	bool gridHalf = false;       // the hash grid's cell is half the limit: chosen from the candidates per moved proxy of the last pair update
 	bool gridForced = false;     // B2HIP_GRID_HALF=0 / 1 fixes it
 	int pairsLargeSticky = 0;    // steps for which the pair update still reads its pair count back before it sorts
@@ -417,10 +408,7 @@ struct b2hip_world
 	bool stepComplete = true;  // b2World::m_stepComplete
 	bool stepSolves = true;    // this call runs Solve (it started from a complete step)
 	bool toiCountersFresh = false, toiSpeculative = false, toiSyncOnly = false, toiNoDomains = false;
-	bool toiRan, toiEventValid, toiChains, toiSerialOnly, kernelTimingLaunches, solverBarriers, colorSmallPending;
-	bool useGraphs;              // replay the host-decision-free launch sequences as hipGraphs (B2HIP_GRAPHS=1)
-	int graphCaptures;
-	GraphSeg segCollide, segIslands, segPairs;
+	bool toiRan, toiEventValid, toiChains, toiSerialOnly, kernelTimingLaunches, colorSmallPending;
 	int hubSteps;
 	int toiFallbacks;                                  // steps whose TOI chains had to be redone serially
 	bool debugTrace;                                   // B2HIP_TRACE=1: hash the body state after every solver stage
@@ -431,7 +419,7 @@ struct b2hip_world
 	long long ktUnitsA, ktUnitsB; // units behind the bandwidth kernels' byte counts (set by b2hip_set_kernel_timing_units)
 	std::vector<hipEvent_t> ktEvents;
 	int ktUsed;          // events recorded this step (pairs)
-	int ktKind;          // 0 none, 1 k_large_velocity, 2 k_solve_small
+	int ktKind;          // 0 none, 1 k_large_velocity, 2 k_solve_small, 4 k_solve_blocks, 5 - 7 (ktBracket), 8 the solver family
 	float ktMs;
 	int ktLaunches;
 	double ktBytes;
@@ -702,51 +690,6 @@ static inline void stampsTaken(b2hip_world* w, const A&, const R&...)
 		}                                                                                     \
 	} while (0)
 
-// ---- hipGraph segments ------------------------------------------------------------------------------
-// The step is ~55 kernels of 2-5 us: issued one by one the host (~3.5 us per launch) is the bottleneck between two
-// read-backs. The three launch sequences that contain no host decision (collide + compaction, island build up to the
-// census read-back, end-of-step pair update) are captured once per world layout and replayed as one graph launch each.
-// A segment is re-captured when anything baked into the kernel arguments changes (the DW pointer block, capacities).
-static uint64_t segSignature(const b2hip_world* w, uint64_t extra)
-{
-	uint64_t h = 1469598103934665603ull ^ extra;
-	h = (h ^ (uint64_t)(uintptr_t)w->scanTmp4.p) * 1099511628211ull;
-	h = (h ^ (uint64_t)(uintptr_t)w->consts.p) * 1099511628211ull;
-	h = (h ^ (uint64_t)(uintptr_t)w->stream) * 1099511628211ull;
-	const unsigned char* p = (const unsigned char*)&w->dw;
-	for (size_t i = 0; i < sizeof(DW); ++i)
-	{
-		h ^= p[i];
-		h *= 1099511628211ull;
-	}
-	return h;
-}
-
-template <typename F>
-static int runSegment(b2hip_world* w, GraphSeg& seg, uint64_t extra, F launches)
-{
-	if (!w->useGraphs || w->debugSync || w->debugTrace) return launches();
-	const uint64_t sig = segSignature(w, extra);
-	if (!seg.exec || seg.sig != sig)
-	{
-		if (seg.exec) (void)hipGraphExecDestroy(seg.exec);
-		if (seg.graph) (void)hipGraphDestroy(seg.graph);
-		seg.exec = nullptr;
-		seg.graph = nullptr;
-		HIP_TRY(hipStreamBeginCapture(w->stream, hipStreamCaptureModeThreadLocal));
-		const int rc = launches();
-		hipError_t e = hipStreamEndCapture(w->stream, &seg.graph);
-		if (rc) return rc;
-		if (e != hipSuccess) return setError(B2HIP_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-		HIP_TRY(hipGraphInstantiate(&seg.exec, seg.graph, nullptr, nullptr, 0));
-		seg.sig = sig;
-		w->graphCaptures += 1;
-	}
-	HIP_TRY(hipGraphLaunch(seg.exec, w->stream));
-	w->dw.stampMask = 0u; // (taken by the first kernel of the segment: the mask is part of the segment's signature)
-	return 0;
-}
-
 static inline bool hasFilter(const b2hip_world* w) { return w->filterFn != nullptr || w->filterBatchFn != nullptr; }
 static inline bool hasPreSolve(const b2hip_world* w) { return w->preSolveFn != nullptr || w->preSolveBatchFn != nullptr; }
 // any listener callback switched on: the TOI sub-steps log their calls (b2hip_get_toi_callbacks) and run in serial order
@@ -801,7 +744,6 @@ static int pollPublished(b2hip_world* w, volatile const int* seq, int want, cons
 	// ... and, as a backstop, after a generous wall-clock deadline (B2HIP_STEP_DEADLINE_S, default 300 s): every device-side
 	// wait is bounded (PERSIST_SPIN_MAX, SCAN_SPIN_MAX), so a stream that stays busy that long is lost, and the caller gets an
 	// error and a failed world instead of a Step() that never returns.
-	static const double deadlineS = getenv("B2HIP_STEP_DEADLINE_S") ? atof(getenv("B2HIP_STEP_DEADLINE_S")) : 300.0;
 	const auto startedAt = std::chrono::steady_clock::now();
 	for (unsigned spins = 1; *seq != want; ++spins)
 	{
@@ -816,7 +758,7 @@ static int pollPublished(b2hip_world* w, volatile const int* seq, int want, cons
 				else if (now - drainedAt > std::chrono::seconds(2)) return setError(B2HIP_ERR_HIP, std::string(what) + " was not published (the stream has drained)");
 			}
 			else drained = false;
-			if (std::chrono::duration<double>(std::chrono::steady_clock::now() - startedAt).count() > deadlineS)
+			if (std::chrono::duration<double>(std::chrono::steady_clock::now() - startedAt).count() > w->stepDeadlineS)
 				return setError(B2HIP_ERR_HIP, std::string(what) + ": the device did not finish the step within the deadline (B2HIP_STEP_DEADLINE_S)");
 		}
 #if defined(__x86_64__)
@@ -839,11 +781,89 @@ static int awaitCensus(b2hip_world* w)
 {
 	// (B2HIP_TEST_POLL_DELAY_US: the host comes late to its poll - what a descheduled thread does to it now and then;
 	// tests/test_gpu_recovery.py: a second publication must not have overwritten the first by then)
-	static const int delayUs = getenv("B2HIP_TEST_POLL_DELAY_US") ? atoi(getenv("B2HIP_TEST_POLL_DELAY_US")) : 0;
-	if (delayUs > 0) std::this_thread::sleep_for(std::chrono::microseconds(delayUs));
+	if (w->pollDelayUs > 0) std::this_thread::sleep_for(std::chrono::microseconds(w->pollDelayUs));
 	if (int rc = pollPublished(w, (volatile const int*)&w->h_pub->pubSeq, w->pubSeq, "island census")) return rc;
 	memcpy(w->h_dstate, w->h_pub, offsetof(DState, pubSeq));
 	return 0;
+}
+
+// ---- the environment switches, read once per world by b2hip_world_create -------------------------------
+static bool envSet(const char* k) { return getenv(k) != nullptr; } // any value
+static bool envOn(const char* k) { const char* e = getenv(k); return e && atoi(e); } // a non-zero number
+static int envInt(const char* k, int unset) { const char* e = getenv(k); return e ? atoi(e) : unset; }
+
+static void readSwitches(b2hip_world* w)
+{
+	DW& d = w->dw;
+	w->debugSync = envSet("B2HIP_DEBUG");
+	w->traceLaunches = envSet("B2HIP_TRACE_LAUNCHES");
+	w->debugTrace = envSet("B2HIP_TRACE");
+	w->forceLarge = envInt("B2HIP_FORCE_LARGE", 0);
+	w->kernelTimingLaunches = envSet("B2HIP_SOLVER_LAUNCHES"); // force the launch-per-colour solver
+	w->noSideStream = envSet("B2HIP_NO_SIDE_STREAM");
+	w->profileDetail = envInt("B2HIP_PROFILE_DETAIL", 1) != 0;
+	if (const char* e = getenv("B2HIP_SOLID_ROUNDS")) { const int v = atoi(e); w->solidRoundsEnv = (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0; }
+	w->collideSplitEnv = envInt("B2HIP_COLLIDE_SPLIT", -1);
+	w->collideUniOff = envInt("B2HIP_COLLIDE_UNI", 1) == 0;
+	w->collideSortEnv = envInt("B2HIP_COLLIDE_SORT", -1);
+	w->collideStage = envInt("B2HIP_COLLIDE_STAGE", -1);
+	w->noSweepBlocks = envSet("B2HIP_NO_SWEEP_BLOCKS");
+	w->tracePartition = envSet("B2HIP_TRACE_PARTITION");
+	w->traceRecovery = envSet("B2HIP_TRACE_RECOVERY");
+	if (const char* e = getenv("B2HIP_GRID_HALF")) { w->gridForced = true; w->gridHalf = atoi(e) != 0; d.gridHalf = w->gridHalf ? 1 : 0; }
+	d.noChainCreate = envSet("B2HIP_TOI_NO_CHAIN_CREATE") ? 1 : 0;
+	d.noOwnIdBlocks = envSet("B2HIP_NO_OWN_ID_BLOCKS") ? 1 : envSet("B2HIP_OWN_ID_BLOCKS_ALL") ? -1 : 0;
+	w->noBlocks = envSet("B2HIP_NO_BLOCKS"); // no block partition at all (colours as before it existed)
+	w->blockLanes = 0; // chosen per partition (see phaseSolve); B2HIP_BLOCK_LANES = 256 | 512 | 1024 forces one size
+	if (const char* e = getenv("B2HIP_BLOCK_LANES")) w->blockLanes = atoi(e) == 512 ? 512 : (atoi(e) == 256 ? 256 : (atoi(e) == 1024 ? 1024 : 0));
+	w->toiSerialOnly = envSet("B2HIP_TOI_SERIAL");
+	w->toiSyncOnly = envSet("B2HIP_TOI_SYNC");
+	w->toiDomWideOnly = envSet("B2HIP_TOI_DOM_WIDE");
+	w->noToiSpecDomains = envSet("B2HIP_TOI_NO_SPEC_DOMAINS");
+	w->debugAssumeFreshGrid = envSet("B2HIP_DEBUG_ASSUME_FRESH_GRID");
+	w->toiNoDomains = envSet("B2HIP_TOI_NO_DOMAINS"); // bullets / kinematic partners through the serial loop only
+	w->toiWhy = envSet("B2HIP_TOI_WHY");
+	w->handoverWhy = envSet("B2HIP_HANDOVER_WHY");
+	w->shardTrace = envOn("B2HIP_SHARD_TRACE");
+	w->recoverOn = !envOn("B2HIP_NO_RECOVER");
+	w->noCensusPoll = envOn("B2HIP_NO_CENSUS_POLL");
+	w->noStatePoll = envOn("B2HIP_NO_STATE_POLL");
+	w->lazyReadback = envOn("B2HIP_LAZY_READBACK");
+	w->earlyRowsMin = envInt("B2HIP_EARLY_ROWS_MIN", w->earlyRowsMin);
+	w->stepDeadlineS = getenv("B2HIP_STEP_DEADLINE_S") ? atof(getenv("B2HIP_STEP_DEADLINE_S")) : 300.0;
+	w->pollDelayUs = envInt("B2HIP_TEST_POLL_DELAY_US", 0);
+	d.bigChunks = envSet("B2HIP_BIG_CHUNKS") ? 1 : 0;
+	// Exact order costs ~1 us per DEPENDENT constraint (a GPU lane against a CPU core on a chain): a 210-box pyramid is
+	// ~300 levels x 12 sweeps = 3.9 ms in k_solve_small, ~0.1 ms as one block of k_solve_blocks. Islands up to 128 (bodies
+	// or contacts) are walked in the reference's order, bit-exact; B2HIP_SMALL_MAX_W (<= 512) moves the line.
+	d.smallMaxW = TINY_ISLAND_MAX_W;
+	if (const char* e = getenv("B2HIP_SMALL_MAX_W")) d.smallMaxW = std::max(1, std::min((int)SMALL_ISLAND_MAX_W, atoi(e)));
+	d.noFreeBodies = envOn("B2HIP_NO_FREE_BODIES") ? 1 : 0;
+	d.testMaxColors = envInt("B2HIP_TEST_MAX_COLORS", 0);
+	d.testColorRounds = envInt("B2HIP_TEST_COLOR_ROUNDS", 0);
+	d.testSpinMax = std::max(0, envInt("B2HIP_TEST_SPIN_MAX", 0));
+	d.restPoll = getenv("B2HIP_REST_POLL") ? std::max(1, std::min(16, atoi(getenv("B2HIP_REST_POLL")))) : 1;
+	d.hubSerial = envOn("B2HIP_HUB_SERIAL") ? 1 : 0;
+	w->hubWaves = envInt("B2HIP_HUB_WAVES", 0) == 1 ? 1 : 8; // (1: the one-wave form, for comparison)
+	// The end of a sweep over islands that run launch per colour - tail colours, hub rows, joints, the verdict of a position
+	// iteration - in one single-workgroup launch (k_sweep_end). B2HIP_NO_SWEEP_END=1: the launches of round 4 (k_large_hub,
+	// k_large_joints, k_large_pos_end); B2HIP_NO_TAIL=1: every colour a launch of its own; B2HIP_HUB_WIDE=0: the hub rows in
+	// k_large_hub's order and scheme (chunks of 64) inside k_sweep_end - what the comparisons in tests/ use. Asking for a
+	// number of hub waves or the serial hub sweep means k_large_hub.
+	w->sweepEnd = !envOn("B2HIP_NO_SWEEP_END") && !envSet("B2HIP_HUB_WAVES");
+	w->sweepTail = w->sweepEnd && !envOn("B2HIP_NO_TAIL");
+	w->sweepStamps = envSet("B2HIP_SWEEP_STAMPS");
+	w->rowMarks = envOn("B2HIP_ROW_MARKS_CHECK") ? 2 : envOn("B2HIP_NO_ROW_MARKS") ? 0 : 1;
+	w->bodyWarm = !envOn("B2HIP_NO_BODY_WARM");
+	w->restFlow = w->sweepEnd && !envOn("B2HIP_NO_REST");
+	w->noHubBuild = envOn("B2HIP_NO_HUB_BUILD");
+	w->noHubOrder = envOn("B2HIP_NO_HUB_ORDER");
+	w->hubOrderAll = envOn("B2HIP_HUB_ORDER");
+	if (getenv("B2HIP_SWEEP_ROWS_MAX")) w->sweepRowsMax = std::max(1, atoi(getenv("B2HIP_SWEEP_ROWS_MAX")));
+	w->restHub = getenv("B2HIP_REST_HUB") ? std::max(0, std::min(2, atoi(getenv("B2HIP_REST_HUB")))) : 2;
+	w->restRowsMax = getenv("B2HIP_REST_ROWS") ? std::min(atoi(getenv("B2HIP_REST_ROWS")), REST_ROWS_MAX - COLOR_SMALL_MAX) : 65536;
+	w->tailRowsMax = envInt("B2HIP_TAIL_ROWS", SWEEP_END_LANES);
+	d.hubWide = (w->sweepEnd && !d.hubSerial && envInt("B2HIP_HUB_WIDE", 1) != 0) ? 1 : 0;
 }
 
 // Size every buffer for the current topology and a contact / pair budget; refresh the kernarg block.
@@ -891,7 +911,7 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 	ENS(b_slot, nb); ENS(b_island, nb); ENS(chunkFirst, (nb + cc) / (TINY_CHUNK_LANES / 2) + 4);
 	ENS(li_bodies, nb); ENS(li_contacts, cc); ENS(li_roots, nb); ENS(li_color, cc);
 	ENS(colorCount, cc + 2 + COLOR_SLOT_PADDED * COLOR_SLOT_STRIDE); ENS(colorStart, cc + 2); ENS(colorCursor, cc + 2 + COLOR_SLOT_PADDED * COLOR_SLOT_STRIDE); ENS(li_sorted, cc); ENS(li_ref, cc); // (colorSlot: the first 65 colour counters on a line each)
-	ENS(bodyClaim, nb); ENS(bodyColorMask, nb); ENS(bodyActive, nb); ENS(bodyRest, nb); ENS(b_posv, nb); ENS(dfRank, B2HIP_HAVE_VALIDATION_SOLVERS ? nb * 32 : 1); ENS(dfInbox, B2HIP_HAVE_VALIDATION_SOLVERS ? 2 * cc : 1); /* (mailbox tables of the test build's k_solve_mailbox: DF_RANKS = 32 slots per body) */ ENS(evKey, cc); ENS(evInfo, cc); ENS(uncolList, COLOR_SMALL_MAX); ENS(compactList, COLOR_SMALL_MAX); ENS(hubRowOf, cc); ENS(hubList, cc); ENS(hubDelta, cc); ENS(hubMeta, 8); ENS(hubFirst, nb); ENS(solveSnapBody, w->recoverOn ? 6 * nb : 1); ENS(solveSnapImp, w->recoverOn ? cc : 1); ENS(solveSnapCFlags, w->recoverOn ? cc : 1); ENS(rootPen, ROOT_PEN_SLOTS * nb); ENS(rootDone, nb); ENS(rootSleepMin, nb);
+	ENS(bodyClaim, nb); ENS(bodyColorMask, nb); ENS(bodyActive, nb); ENS(bodyRest, nb); ENS(b_posv, nb); ENS(evKey, cc); ENS(evInfo, cc); ENS(uncolList, COLOR_SMALL_MAX); ENS(compactList, COLOR_SMALL_MAX); ENS(hubRowOf, cc); ENS(hubList, cc); ENS(hubDelta, cc); ENS(hubMeta, 8); ENS(hubFirst, nb); ENS(solveSnapBody, w->recoverOn ? 6 * nb : 1); ENS(solveSnapImp, w->recoverOn ? cc : 1); ENS(solveSnapCFlags, w->recoverOn ? cc : 1); ENS(rootPen, ROOT_PEN_SLOTS * nb); ENS(rootDone, nb); ENS(rootSleepMin, nb);
 	if (w->lc.cap < (size_t)LC_WORDS * cc)
 	{
 		rc = w->lc.ensure((size_t)LC_WORDS * cc, s, false, false);
@@ -959,42 +979,6 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 	d.nProxies = (int)w->fixtures.size();
 	d.nJoints = (int)w->joints.size();
 	d.nShapes = (int)w->shapes.size();
-	d.bigChunks = getenv("B2HIP_BIG_CHUNKS") != nullptr ? 1 : 0;
-	// Exact order costs ~1 us per DEPENDENT constraint (a GPU lane against a CPU core on a chain): a 210-box pyramid is
-	// ~300 levels x 12 sweeps = 3.9 ms in k_solve_small, ~0.1 ms as one block of k_solve_blocks. Islands up to 128 (bodies
-	// or contacts) are walked in the reference's order, bit-exact; B2HIP_SMALL_MAX_W (<= 512) moves the line.
-	d.smallMaxW = TINY_ISLAND_MAX_W;
-	d.noFreeBodies = getenv("B2HIP_NO_FREE_BODIES") && atoi(getenv("B2HIP_NO_FREE_BODIES")) ? 1 : 0;
-	d.testMaxColors = getenv("B2HIP_TEST_MAX_COLORS") ? atoi(getenv("B2HIP_TEST_MAX_COLORS")) : 0;
-	d.testColorRounds = getenv("B2HIP_TEST_COLOR_ROUNDS") ? atoi(getenv("B2HIP_TEST_COLOR_ROUNDS")) : 0;
-	d.testSpinMax = getenv("B2HIP_TEST_SPIN_MAX") ? std::max(0, atoi(getenv("B2HIP_TEST_SPIN_MAX"))) : 0;
-	d.restPoll = getenv("B2HIP_REST_POLL") ? std::max(1, std::min(16, atoi(getenv("B2HIP_REST_POLL")))) : 1;
-	d.hubSerial = getenv("B2HIP_HUB_SERIAL") && atoi(getenv("B2HIP_HUB_SERIAL")) ? 1 : 0;
-	w->hubWaves = getenv("B2HIP_HUB_WAVES") && atoi(getenv("B2HIP_HUB_WAVES")) == 1 ? 1 : 8; // (1: the one-wave form, for comparison)
-	// The end of a sweep over islands that run launch per colour - tail colours, hub rows, joints, the verdict of a position
-	// iteration - in one single-workgroup launch (k_sweep_end). B2HIP_NO_SWEEP_END=1: the launches of round 4 (k_large_hub,
-	// k_large_joints, k_large_pos_end); B2HIP_NO_TAIL=1: every colour a launch of its own; B2HIP_HUB_WIDE=0: the hub rows in
-	// k_large_hub's order and scheme (chunks of 64) inside k_sweep_end - what the comparisons in tests/ use. Asking for a
-	// number of hub waves or the serial hub sweep means k_large_hub.
-	w->sweepEnd = !(getenv("B2HIP_NO_SWEEP_END") && atoi(getenv("B2HIP_NO_SWEEP_END"))) && !getenv("B2HIP_HUB_WAVES");
-	w->sweepTail = w->sweepEnd && !(getenv("B2HIP_NO_TAIL") && atoi(getenv("B2HIP_NO_TAIL")));
-	w->recolorSlack = getenv("B2HIP_RECOLOR_SLACK") ? atoi(getenv("B2HIP_RECOLOR_SLACK")) : 2;
-	w->sweepStamps = getenv("B2HIP_SWEEP_STAMPS") != nullptr;
-	w->rowMarks = (getenv("B2HIP_ROW_MARKS_CHECK") && atoi(getenv("B2HIP_ROW_MARKS_CHECK"))) ? 2 : (getenv("B2HIP_NO_ROW_MARKS") && atoi(getenv("B2HIP_NO_ROW_MARKS"))) ? 0 : 1;
-	w->bodyWarm = !(getenv("B2HIP_NO_BODY_WARM") && atoi(getenv("B2HIP_NO_BODY_WARM")));
-	w->restFlow = w->sweepEnd && !(getenv("B2HIP_NO_REST") && atoi(getenv("B2HIP_NO_REST")));
-	w->noHubBuild = getenv("B2HIP_NO_HUB_BUILD") && atoi(getenv("B2HIP_NO_HUB_BUILD"));
-	w->noHubOrder = getenv("B2HIP_NO_HUB_ORDER") && atoi(getenv("B2HIP_NO_HUB_ORDER"));
-	w->hubOrderAll = getenv("B2HIP_HUB_ORDER") && atoi(getenv("B2HIP_HUB_ORDER"));
-	w->colorAheadOff = getenv("B2HIP_NO_COLOR_AHEAD") && atoi(getenv("B2HIP_NO_COLOR_AHEAD"));
-	w->noCensusGrid = getenv("B2HIP_NO_CENSUS_GRID") && atoi(getenv("B2HIP_NO_CENSUS_GRID"));
-	if (const char* e = getenv("B2HIP_COLOR_LANES")) { const int v = atoi(e); w->colorLanes = v == 64 ? 64 : (v == 128 ? 128 : 256); }
-	if (getenv("B2HIP_SWEEP_ROWS_MAX")) w->sweepRowsMax = std::max(1, atoi(getenv("B2HIP_SWEEP_ROWS_MAX")));
-	w->restHub = getenv("B2HIP_REST_HUB") ? std::max(0, std::min(2, atoi(getenv("B2HIP_REST_HUB")))) : 2;
-	w->restRowsMax = getenv("B2HIP_REST_ROWS") ? std::min(atoi(getenv("B2HIP_REST_ROWS")), REST_ROWS_MAX - COLOR_SMALL_MAX) : 65536;
-	w->tailRowsMax = getenv("B2HIP_TAIL_ROWS") ? atoi(getenv("B2HIP_TAIL_ROWS")) : SWEEP_END_LANES;
-	d.hubWide = (w->sweepEnd && !d.hubSerial && !(getenv("B2HIP_HUB_WIDE") && atoi(getenv("B2HIP_HUB_WIDE")) == 0)) ? 1 : 0;
-	if (const char* e = getenv("B2HIP_SMALL_MAX_W")) d.smallMaxW = std::max(1, std::min((int)SMALL_ISLAND_MAX_W, atoi(e)));
 	d.capContacts = (int)cc;
 	d.capPairs = (int)w->pairKey.cap;
 	d.capMoves = (int)w->moveBuf.cap;
@@ -1025,7 +1009,7 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 	d.chunkFirst = w->chunkFirst.p;
 	d.li_bodies = w->li_bodies.p; d.li_contacts = w->li_contacts.p; d.li_roots = w->li_roots.p; d.li_color = w->li_color.p;
 	d.colorCount = w->colorCount.p; d.colorStart = w->colorStart.p; d.colorCursor = w->colorCursor.p; d.li_sorted = w->li_sorted.p; d.li_ref = w->li_ref.p;
-	d.bodyClaim = w->bodyClaim.p; d.bodyColorMask = w->bodyColorMask.p; d.bodyActive = w->bodyActive.p; d.bodyRest = w->bodyRest.p; d.b_posv = w->b_posv.p; d.dfRank = w->dfRank.p; d.dfInbox = w->dfInbox.p; d.evKey = w->evKey.p; d.evInfo = w->evInfo.p; d.eventsOn = w->eventsOn ? 1 : 0; d.uncolList = w->uncolList.p; d.compactList = w->compactList.p; d.hubRowOf = w->hubRowOf.p; d.hubList = w->hubList.p; d.hubDelta = w->hubDelta.p; d.hubMeta = w->hubMeta.p; d.hubFirst = w->hubFirst.p; d.lc = w->lc.p; d.warmDelta = w->warmDelta.p; d.rootPen = w->rootPen.p;
+	d.bodyClaim = w->bodyClaim.p; d.bodyColorMask = w->bodyColorMask.p; d.bodyActive = w->bodyActive.p; d.bodyRest = w->bodyRest.p; d.b_posv = w->b_posv.p; d.dfRank = nullptr; d.dfInbox = nullptr; d.evKey = w->evKey.p; d.evInfo = w->evInfo.p; d.eventsOn = w->eventsOn ? 1 : 0; d.uncolList = w->uncolList.p; d.compactList = w->compactList.p; d.hubRowOf = w->hubRowOf.p; d.hubList = w->hubList.p; d.hubDelta = w->hubDelta.p; d.hubMeta = w->hubMeta.p; d.hubFirst = w->hubFirst.p; d.lc = w->lc.p; d.warmDelta = w->warmDelta.p; d.rootPen = w->rootPen.p;
 	d.rootDone = w->rootDone.p; d.rootSleepMin = w->rootSleepMin.p;
 	d.moveBuf = w->moveBuf.p; d.gridCount = w->gridCount.p; d.gridStart = w->gridStart.p; d.gridCursor = w->gridCursor.p;
 	d.gridItems = w->gridItems.p; d.gridFat = w->gridFat.p; d.arriveTree = w->arriveTree.p; d.largeProxies = w->largeProxies.p; d.largeMoves = w->largeMoves.p;

@@ -122,8 +122,8 @@ def test_a_host_that_polls_late_still_gets_the_census(amd, monkeypatch):
     """A world without a partition publishes twice per step: the island census (k_block_census) and, a few microseconds to
     ~80 us later, the state behind k_color_small. Into ONE buffer with ONE count (as first built in round 6) a host that
     reached its poll late found the second number where it waited for the first - "island census was not published", one
-    step in a few hundred on a busy box. Two buffers, two counts now; here the host is MADE late (the delay is read once per
-    process, so this test only proves something in a process that has not polled before - it still must pass in any)."""
+    step in a few hundred on a busy box. Two buffers, two counts now; here the host is MADE late (the delay is read when the
+    world is created)."""
     monkeypatch.setenv("B2HIP_TEST_POLL_DELAY_US", "300")
     late, s1, _ = run(amd, monkeypatch, bh.TUMBLER, 80, {"B2HIP_NO_BLOCKS": "1"}, p0=60)
     monkeypatch.delenv("B2HIP_TEST_POLL_DELAY_US", raising=False)
