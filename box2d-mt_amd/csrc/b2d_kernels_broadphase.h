@@ -141,12 +141,14 @@ __device__ __forceinline__ bool gridWindow(const DW& W, float4 a, int* ix0, int*
 }
 
 // force = 1: rebuild the grid although the move buffer is empty (the TOI phase queries it and needs it to reflect
-// every fat AABB as of now; the pair census of the finished pair update is left alone)
+// every fat AABB as of now; the pair census of the finished pair update is left alone); force = 2: the same, also when
+// Counters::gridFresh says this step's pair update built it (the batched queries between steps: the TOI phase and host
+// edits may have moved boxes since, and neither clears the flag)
 __global__ __launch_bounds__(256) void k_grid_clear(DW W, int force)
 {
 	b2dPhaseStamp(W);
 	DState* S = W.st;
-	if (force && S->c.gridFresh) return; // (this step's pair update built it, nothing has moved since)
+	if (force == 1 && S->c.gridFresh) return; // (this step's pair update built it, nothing has moved since)
 	// always reset the pair census, also when nothing moved: the ordering / creation kernels that
 	// follow key off nPairs and must see 0 then
 	if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -171,7 +173,7 @@ __global__ __launch_bounds__(256) void k_grid_count(DW W, int force)
 	b2dPhaseStamp(W);
 	DState* S = W.st;
 	if (S->c.nMoves == 0 && !force) return;
-	if (force && S->c.gridFresh) return;
+	if (force == 1 && S->c.gridFresh) return;
 	const int n = W.nProxies;
 	for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x)
 	{
@@ -196,7 +198,7 @@ __global__ __launch_bounds__(256) void k_grid_fill(DW W, int force)
 	b2dPhaseStamp(W);
 	DState* S = W.st;
 	if (S->c.nMoves == 0 && !force) return;
-	if (force && S->c.gridFresh) return;
+	if (force == 1 && S->c.gridFresh) return;
 	const int n = W.nProxies;
 	for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x)
 	{

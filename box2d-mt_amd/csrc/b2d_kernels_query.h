@@ -1,0 +1,379 @@
+// b2d_kernels_query.h - batched world queries between steps (b2hip_query_aabbs / b2hip_query_points / b2hip_ray_cast_closest).
+//
+// Everything is read from the world's device state: the fat AABBs, the proxies' filters and shapes, the bodies' transforms,
+// and the hashed grid of b2d_kernels_broadphase.h, rebuilt from every proxy's box just before (gridRebuildNow). One WAVE per
+// query. A proxy is binned in the cell of its centre and is at most gridLimit wide, so every proxy whose box overlaps the
+// query box has its centre in the query box grown by half the limit: the cells of gridWindow. Cells of a window that hash to
+// the same bucket would show a proxy twice; a candidate counts only in the cell its own centre lies in (the bucket dedup).
+// Proxies wider than the limit (DW::largeProxies) are tested by every query.
+//
+// Determinism: the grid's order inside a bucket depends on arrival, so nothing here depends on it. Box and point queries
+// sort each query's items by fixture id (k_query_sort, k_query_compact_big); rays keep the smallest (fraction bits, fixture)
+// key, a total order.
+#ifndef B2D_KERNELS_QUERY_H
+#define B2D_KERNELS_QUERY_H
+
+#include "b2d_kernels_broadphase.h"
+#include "b2d_kernels_collide.h"
+#include "b2d_shape_geom.h"
+
+#define QUERY_WINDOW_MAX 4096     // cells a window may have; a wider one scans every proxy
+#define QUERY_COORD_MAX 1.0e8f    // coordinates beyond this (in magnitude) scan every proxy too (no cell index overflows)
+#define QUERY_SORT_MAX 4096       // items of one query sorted in LDS by k_query_sort; more: k_query_mark + k_query_compact_big
+#define QUERY_SORT_THREADS 256
+
+// b2hip_query_filter on the proxy's filter words (DW::p_filter0 low half = categoryBits, p_filter1 PF_SENSOR)
+__device__ __forceinline__ bool queryFilterPasses(const DW& W, int q, uint32_t mask, int sensors)
+{
+	return (W.p_filter0[q] & mask & 0xffffu) != 0u && (sensors || (W.p_filter1[q] & PF_SENSOR) == 0);
+}
+
+__device__ __forceinline__ bool queryBoxSane(float4 b)
+{
+	return fabsf(b.x) <= QUERY_COORD_MAX && fabsf(b.y) <= QUERY_COORD_MAX && fabsf(b.z) <= QUERY_COORD_MAX && fabsf(b.w) <= QUERY_COORD_MAX;
+}
+
+// Calls visit(valid, proxy, fatAabb) for every grid-sized proxy binned in a cell of box's window, 64 candidates per call,
+// whole wave (the lanes' candidates: valid = false on lanes without one). The cells are taken 64 at a time, lane c owning
+// cell c; their counts are flattened into one index space by a prefix sum over the lanes, and candidate idx finds its cell
+// by a binary search over those sums (as k_find_pairs_window does). false: the window is too wide / degenerate - the caller
+// scans every proxy instead (queryVisitAll).
+template <typename F>
+__device__ __forceinline__ bool queryVisitGrid(const DW& W, int lane, float4 box, F& visit)
+{
+	int ix0, iy0, nx, ny;
+	if (!queryBoxSane(box) || !gridWindow(W, box, &ix0, &iy0, &nx, &ny)) return false;
+	const int nCells = nx * ny;
+	if (nCells > QUERY_WINDOW_MAX) return false;
+	for (int c0 = 0; c0 < nCells; c0 += 64)
+	{
+		const int c = c0 + lane;
+		int cx = 0, cy = 0, cnt = 0, start = 0;
+		if (c < nCells)
+		{
+			cx = ix0 + c % nx;
+			cy = iy0 + c / nx;
+			const uint32_t h = cellHash(cx, cy, W.gridMask);
+			cnt = W.gridCount[h];
+			start = W.gridStart[h];
+		}
+		int incl = cnt;
+		for (int off = 1; off < 64; off <<= 1)
+		{
+			const int v = __shfl_up(incl, off);
+			if (lane >= off) incl += v;
+		}
+		const int excl = incl - cnt;
+		const int total = __shfl(incl, 63);
+		for (int base = 0; base < total; base += 64)
+		{
+			const int idx = base + lane;
+			int lo = 0, hi = 63;
+#pragma unroll
+			for (int step = 0; step < 6; ++step)
+			{
+				const int mid = (lo + hi) >> 1;
+				if (__shfl(incl, mid) > idx) hi = mid; else lo = mid + 1;
+			}
+			const int cl = lo < 63 ? lo : 63;
+			const int t = __shfl(start, cl) + (idx - __shfl(excl, cl));
+			const int cellX = __shfl(cx, cl), cellY = __shfl(cy, cl);
+			bool valid = idx < total;
+			int q = -1;
+			float4 fat = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+			if (valid)
+			{
+				q = W.gridItems[t];
+				fat = W.gridFat[t];
+				int px, py;
+				proxyCell(W, fat, &px, &py);
+				valid = px == cellX && py == cellY; // (the bucket dedup)
+			}
+			visit(valid, q, fat);
+		}
+	}
+	return true;
+}
+
+template <typename F>
+__device__ __forceinline__ void queryVisitLarge(const DW& W, int lane, F& visit)
+{
+	const int nLarge = W.st->c.nLargeProxies;
+	for (int base = 0; base < nLarge; base += 64)
+	{
+		const int k = base + lane;
+		const int q = k < nLarge ? W.largeProxies[k] : -1;
+		visit(q >= 0, q, q >= 0 ? W.p_fat[q] : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+	}
+}
+
+// every live proxy (grid-sized and large)
+template <typename F>
+__device__ __forceinline__ void queryVisitAll(const DW& W, int lane, F& visit)
+{
+	for (int base = 0; base < W.nProxies; base += 64)
+	{
+		const int q = base + lane;
+		const bool live = q < W.nProxies && W.p_body[q] >= 0;
+		visit(live, q, live ? W.p_fat[q] : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+	}
+}
+
+// Box and point queries. pass 0: counts[i] = items of query i; pass 1: query i's items (fixture ids, unsorted) at
+// items[offsets[i] ...]. points: boxes[i] = (x, y, x, y) and the shape must contain the point (b2dShapeTestPoint).
+template <int PASS, bool POINTS>
+__device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, int n, uint32_t mask, int sensors, int* counts,
+                                               const int* offsets, int* items)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const int nWaves = (int)((gridDim.x * blockDim.x) >> 6);
+	for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nWaves)
+	{
+		const float4 b = boxes[i];
+		if (!(b.x <= b.z && b.y <= b.w)) // (lower > upper, or a NaN: nothing)
+		{
+			if (PASS == 0 && lane == 0) counts[i] = 0;
+			continue;
+		}
+		AABB a;
+		a.lo = v2(b.x, b.y);
+		a.hi = v2(b.z, b.w);
+		int found = 0;
+		const int at = PASS == 1 ? offsets[i] : 0, end = PASS == 1 ? offsets[i + 1] : 0;
+		auto visit = [&](bool valid, int q, float4 fat)
+		{
+			bool hit = false;
+			if (valid)
+			{
+				AABB f;
+				f.lo = v2(fat.x, fat.y);
+				f.hi = v2(fat.z, fat.w);
+				hit = b2dAabbOverlap(a, f) && queryFilterPasses(W, q, mask, sensors);
+				if (POINTS && hit) hit = b2dShapeTestPoint(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), a.lo);
+			}
+			const unsigned long long m = __ballot(hit);
+			if (PASS == 1 && hit)
+			{
+				const int k = at + found + (int)__popcll(m & ((1ull << lane) - 1ull));
+				if (k < end) items[k] = q;
+			}
+			found += (int)__popcll(m);
+		};
+		if (queryVisitGrid(W, lane, b, visit)) queryVisitLarge(W, lane, visit);
+		else queryVisitAll(W, lane, visit);
+		if (PASS == 0 && lane == 0) counts[i] = found;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_query_aabbs_count(DW W, const float4* boxes, int n, uint32_t mask, int sensors, int* counts)
+{
+	queryBoxesWave<0, false>(W, boxes, n, mask, sensors, counts, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void k_query_aabbs_fill(DW W, const float4* boxes, int n, uint32_t mask, int sensors, const int* offsets, int* items)
+{
+	queryBoxesWave<1, false>(W, boxes, n, mask, sensors, nullptr, offsets, items);
+}
+__global__ __launch_bounds__(256) void k_query_points_count(DW W, const float4* boxes, int n, uint32_t mask, int sensors, int* counts)
+{
+	queryBoxesWave<0, true>(W, boxes, n, mask, sensors, counts, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void k_query_points_fill(DW W, const float4* boxes, int n, uint32_t mask, int sensors, const int* offsets, int* items)
+{
+	queryBoxesWave<1, true>(W, boxes, n, mask, sensors, nullptr, offsets, items);
+}
+
+// One workgroup per query: its items sorted ascending in LDS (bitonic network over the next power of two, padded with
+// INT_MAX). Lists longer than QUERY_SORT_MAX are left to k_query_mark / k_query_compact_big.
+__global__ __launch_bounds__(QUERY_SORT_THREADS) void k_query_sort(const int* offsets, int n, int* items)
+{
+	__shared__ int s[QUERY_SORT_MAX];
+	for (int i = blockIdx.x; i < n; i += gridDim.x)
+	{
+		const int at = offsets[i], len = offsets[i + 1] - at;
+		if (len <= 1 || len > QUERY_SORT_MAX) continue;
+		int size = 2;
+		while (size < len) size <<= 1;
+		for (int k = threadIdx.x; k < size; k += blockDim.x) s[k] = k < len ? items[at + k] : 0x7fffffff;
+		__syncthreads();
+		for (int span = 2; span <= size; span <<= 1)
+		{
+			for (int j = span >> 1; j > 0; j >>= 1)
+			{
+				for (int k = threadIdx.x; k < size; k += blockDim.x)
+				{
+					const int other = k ^ j;
+					if (other > k)
+					{
+						const int x = s[k], y = s[other];
+						const bool up = (k & span) == 0;
+						if (up ? x > y : x < y)
+						{
+							s[k] = y;
+							s[other] = x;
+						}
+					}
+				}
+				__syncthreads();
+			}
+		}
+		for (int k = threadIdx.x; k < len; k += blockDim.x) items[at + k] = s[k];
+		__syncthreads();
+	}
+}
+
+// A query with more than QUERY_SORT_MAX items (a box over much of the world): its fixture ids - distinct - are marked in a
+// flag per proxy, and k_query_compact_big writes the marked ids back in proxy order, clearing the flags behind it. Cost: two
+// launches per such query, one after the other from the host, and ONE workgroup walking all nProxies flags - a batch of k
+// wide boxes on a world of N proxies costs k x N flag reads on one CU (10^6 proxies: 1 000 rounds of 1 024 flags per query).
+__global__ __launch_bounds__(256) void k_query_mark(const int* items, int len, int* flags)
+{
+	for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < len; k += gridDim.x * blockDim.x) flags[items[k]] = 1;
+}
+__global__ __launch_bounds__(1024) void k_query_compact_big(int* flags, int nProxies, int* out)
+{
+	__shared__ int s_wave[16];
+	__shared__ int s_run;
+	const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+	if (tid == 0) s_run = 0;
+	__syncthreads();
+	for (int base = 0; base < nProxies; base += 1024)
+	{
+		const int p = base + tid;
+		const bool on = p < nProxies && flags[p] != 0;
+		const unsigned long long m = __ballot(on);
+		if (lane == 0) s_wave[wv] = (int)__popcll(m);
+		__syncthreads();
+		int before = s_run;
+		for (int q = 0; q < wv; ++q) before += s_wave[q];
+		if (on)
+		{
+			out[before + (int)__popcll(m & ((1ull << lane) - 1ull))] = p;
+			flags[p] = 0;
+		}
+		__syncthreads();
+		if (tid == 0)
+		{
+			int add = 0;
+			for (int q = 0; q < 16; ++q) add += s_wave[q];
+			s_run += add;
+		}
+		__syncthreads();
+	}
+}
+
+// Closest ray hit, one WAVE per ray. The ray is cut into pieces about a cell long; the cells of a piece's box (grown by
+// half the grid limit, gridWindow) hold every grid-sized proxy whose box the piece can meet, so after piece k every hit at
+// a fraction up to its end t1 has been seen: the walk stops once the best fraction is below t1. Large proxies are tested
+// by every ray. A candidate is culled by the segment against its fat AABB (b2DynamicTree::RayCast's two tests, the box
+// grown by a margin that covers rounding: only boxes the reference culls as well), then cast against its shape at the
+// body's transform with maxFraction 1 (the fraction and normal of a hit do not depend on maxFraction). Best = the smallest
+// (fraction bits, fixture id): fractions are >= 0 (a -0.0 enters as +0.0), so their bits order like the values, and ties
+// go to the lower id. A ray of more than QUERY_WINDOW_MAX pieces (or with a coordinate beyond QUERY_COORD_MAX) tests every
+// proxy of the world from its one wave instead: 10^6 candidates on a 10^6-body world - a scan is still cheaper than
+// thousands of pieces, but it is the slow case of this kernel.
+__device__ __forceinline__ unsigned long long waveMinU64(unsigned long long v)
+{
+	for (int off = 32; off > 0; off >>= 1)
+	{
+		const unsigned long long o = __shfl_xor(v, off);
+		v = o < v ? o : v;
+	}
+	return v;
+}
+
+__global__ __launch_bounds__(256) void k_query_rays(DW W, const float4* rays, int n, uint32_t mask, int sensors, b2hip_ray_hit* out)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const int nWaves = (int)((gridDim.x * blockDim.x) >> 6);
+	for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nWaves)
+	{
+		const float4 r = rays[i];
+		const V2 p1 = v2(r.x, r.y), p2 = v2(r.z, r.w);
+		const V2 d = p2 - p1;
+		unsigned long long best = ~0ull;
+		const bool finite = isfinite(r.x) && isfinite(r.y) && isfinite(r.z) && isfinite(r.w);
+		if (finite && (d.x != 0.0f || d.y != 0.0f))
+		{
+			const float mag = fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fmaxf(fabsf(r.z), fabsf(r.w)));
+			const float eps = 1.0e-3f + 1.0e-5f * mag;
+			const float len = sqrtf(d.x * d.x + d.y * d.y);
+			const V2 u = v2(d.x / len, d.y / len);
+			const V2 perp = v2(-u.y, u.x), aperp = v2(fabsf(perp.x), fabsf(perp.y));
+			const V2 slo = v2(fminf(p1.x, p2.x) - eps, fminf(p1.y, p2.y) - eps);
+			const V2 shi = v2(fmaxf(p1.x, p2.x) + eps, fmaxf(p1.y, p2.y) + eps);
+			auto visit = [&](bool valid, int q, float4 fat)
+			{
+				bool cand = valid && !(fat.x > shi.x || fat.y > shi.y || slo.x > fat.z || slo.y > fat.w);
+				if (cand)
+				{
+					const V2 c = v2(0.5f * (fat.x + fat.z), 0.5f * (fat.y + fat.w));
+					const V2 h = v2(0.5f * (fat.z - fat.x) + eps, 0.5f * (fat.w - fat.y) + eps);
+					const V2 rel = p1 - c;
+					cand = fabsf(perp.x * rel.x + perp.y * rel.y) - (aperp.x * h.x + aperp.y * h.y) <= 0.0f;
+				}
+				if (cand) cand = queryFilterPasses(W, q, mask, sensors);
+				if (cand)
+				{
+					RayHit hit;
+					if (b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), p1, p2, 1.0f, &hit))
+					{
+						// (+ 0.0f: a ray that starts on an edge or a circle is hit at -0.0, whose bits would sort after
+						// every positive fraction; the kept hit's own fraction, -0.0 included, is reported below)
+						const unsigned long long key = ((unsigned long long)__float_as_uint(hit.fraction + 0.0f) << 32) | (uint32_t)q;
+						best = key < best ? key : best;
+					}
+				}
+			};
+			queryVisitLarge(W, lane, visit);
+			const float cell = gridCell(W);
+			const float pieces = ceilf(len / cell);
+			bool all = !(pieces <= (float)QUERY_WINDOW_MAX) || !(mag <= QUERY_COORD_MAX);
+			if (!all)
+			{
+				const int np = pieces < 1.0f ? 1 : (int)pieces;
+				for (int k = 0; k < np; ++k)
+				{
+					const float t0 = (float)k / (float)np, t1 = k + 1 == np ? 1.0f : (float)(k + 1) / (float)np;
+					const V2 a = p1 + t0 * d, b = k + 1 == np ? p2 : p1 + t1 * d;
+					const float4 box = make_float4(fminf(a.x, b.x) - eps, fminf(a.y, b.y) - eps, fmaxf(a.x, b.x) + eps, fmaxf(a.y, b.y) + eps);
+					if (!queryVisitGrid(W, lane, box, visit))
+					{
+						all = true;
+						break;
+					}
+					best = waveMinU64(best);
+					if (best != ~0ull && __uint_as_float((uint32_t)(best >> 32)) < t1) break;
+				}
+			}
+			if (all) queryVisitAll(W, lane, visit);
+			best = waveMinU64(best);
+		}
+		if (lane == 0)
+		{
+			b2hip_ray_hit o;
+			o.fixture = -1;
+			o.body = -1;
+			o.point_x = o.point_y = o.normal_x = o.normal_y = 0.0f;
+			o.fraction = 1.0f;
+			o.pad = 0;
+			if (best != ~0ull)
+			{
+				const int q = (int)(uint32_t)best;
+				const int body = W.p_body[q];
+				RayHit hit;
+				(void)b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, body), p1, p2, 1.0f, &hit); // (the kept hit again: its normal)
+				const float f = hit.fraction;
+				o.fixture = q;
+				o.body = body;
+				o.point_x = (1.0f - f) * p1.x + f * p2.x;
+				o.point_y = (1.0f - f) * p1.y + f * p2.y;
+				o.normal_x = hit.normal.x;
+				o.normal_y = hit.normal.y;
+				o.fraction = f;
+			}
+			out[i] = o;
+		}
+	}
+}
+
+#endif

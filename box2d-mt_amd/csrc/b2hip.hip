@@ -32,6 +32,7 @@
 #include "b2d_kernels_edit.h"
 #include "b2d_kernels_shard.h"
 #include "b2d_kernels_spatial.h"
+#include "b2d_kernels_query.h"
 #include "b2d_scan.h"
 #include "b2d_shape_geom.h"
 
@@ -48,4 +49,5 @@ extern "C"
 #include "b2hip_api_snapshot.h"
 #include "b2hip_api_sharding.h"
 #include "b2hip_api_callbacks.h"
+#include "b2hip_api_query.h"
 } // extern "C"

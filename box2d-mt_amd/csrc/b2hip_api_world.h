@@ -232,6 +232,9 @@ void b2hip_world_destroy(b2hip_world* w)
 	w->blkBodyStart.release(); w->blkBodies.release(); w->rowColor.release(); w->b_cutv.release();
 	w->pairFirst.release(); w->pairRank.release(); w->scanTmp.release(); w->radixHist.release(); w->radixHistScan.release();
 	w->keepFlag.release(); w->keepScan.release(); w->scanTmp4.release(); w->scanFlags.release(); w->stateOut.release(); w->consts.release();
+	w->qIn.release(); w->qCounts.release(); w->qOffsets.release(); w->qItems.release(); w->qFlags.release(); w->qScanWork.release();
+	w->qScanWords.release(); w->qWords.release(); w->qHits.release();
+	if (w->qPinned) (void)hipHostFree(w->qPinned);
 	if (w->h_state) (void)hipHostFree(w->h_state);
 	if (w->h_dstate) (void)hipHostFree(w->h_dstate);
 	if (w->h_pub) (void)hipHostFree(w->h_pub);

@@ -1208,6 +1208,19 @@ static int toiBuildAdjacency(b2hip_world* w, hipStream_t s)
 	return 0;
 }
 
+// Makes the hash grid reflect every proxy's fat AABB as of now, without touching the pair census (k_grid_clear): force 1
+// unless Counters::gridFresh says it already does (the TOI phase), force 2 whatever it says (the batched queries, with a
+// scan context of their own: `sf`).
+static int gridRebuildNow(b2hip_world* w, int force, ScanFlags& sf)
+{
+	DW& d = w->dw;
+	LAUNCH(w, k_grid_clear, gridFor(d.gridMask + 1), 256, d, force);
+	LAUNCH(w, k_grid_count, gridFor(d.nProxies), 256, d, force);
+	deviceExclusiveScan<int>(w->stream, d.gridCount, d.gridStart, d.scanTmp, sf, w->consts.p + 1, (int)(d.gridMask + 1));
+	LAUNCH(w, k_grid_fill, gridFor(d.nProxies), 256, d, force);
+	return 0;
+}
+
 static int toiBuildIndexes(b2hip_world* w, bool csr, bool gridKnownFresh = false)
 {
 	DW& d = w->dw;
@@ -1222,11 +1235,7 @@ static int toiBuildIndexes(b2hip_world* w, bool csr, bool gridKnownFresh = false
 	// host saves their launches when the read-back it already has says so: 128 us of a million-proxy world's step)
 	// (a sharded rank launches them anyway: other ranks' boxes may have arrived since the host last looked - the kernels know)
 	if (gridKnownFresh && !w->spatial) return 0;
-	LAUNCH(w, k_grid_clear, gridFor(d.gridMask + 1), 256, d, 1);
-	LAUNCH(w, k_grid_count, gridFor(d.nProxies), 256, d, 1);
-	deviceExclusiveScan<int>(w->stream, d.gridCount, d.gridStart, d.scanTmp, w->scanCtx, w->consts.p + 1, (int)(d.gridMask + 1));
-	LAUNCH(w, k_grid_fill, gridFor(d.nProxies), 256, d, 1);
-	return 0;
+	return gridRebuildNow(w, 1, w->scanCtx);
 }
 
 static int toiSerial(b2hip_world* w)

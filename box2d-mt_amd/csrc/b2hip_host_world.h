@@ -192,6 +192,14 @@ struct b2hip_world
 	DevArray<int> pairFirst, pairRank;
 	DevArray<int> scanTmp, radixHist, radixHistScan, keepFlag, keepScan;
 	DevArray<int4> scanTmp4;
+	// batched queries (b2hip_api_query.h): the batch and its results on the device, a pinned staging buffer for the copies,
+	// scan scratch of their own (the step's scan context reports a look-back failure into Counters::overflow); grown on demand
+	DevArray<float4> qIn;
+	DevArray<int> qCounts, qOffsets, qItems, qFlags, qScanWork, qScanWords, qWords;
+	DevArray<b2hip_ray_hit> qHits;
+	ScanFlags qScan;
+	void* qPinned = nullptr;
+	size_t qPinnedBytes = 0;
 	void* shardComm = nullptr;   // ncclComm_t of a connected sharded world (b2hip_shard_connect)
 	DevArray<int> shardSend, shardRecv; // this rank's slab / all ranks' slabs
 	size_t shardExchangeBytes = 0;

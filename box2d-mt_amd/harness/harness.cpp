@@ -459,6 +459,160 @@ int b2h_raycast_closest(b2h_world* h, float x1, float y1, float x2, float y2, fl
 	return 1;
 }
 
+#if defined(B2H_BACKEND_AMD)
+// Device fixture id -> (body, fixture index in body) in out2[2 * id]; a chain's children share their fixture's row. Ids
+// nobody owns (destroyed, inactive) read -1. Returns the number of device fixture ids (the batched device queries report
+// these ids: tests/test_gpu_queries_batch.py maps them onto this harness's rows).
+int b2h_device_fixture_rows(b2h_world* h, int cap, int* out2)
+{
+	int n = 0;
+	for (size_t i = 0; i < h->scene.bodies.size(); ++i)
+		if (h->scene.bodies[i])
+			for (const b2Fixture* f = h->scene.bodies[i]->GetFixtureList(); f; f = f->GetNext())
+				n = std::max(n, (int)(f->GetDeviceId() + f->GetShape()->GetChildCount()));
+	for (int k = 0; k < std::min(n, cap); ++k) out2[2 * k] = out2[2 * k + 1] = -1;
+	for (size_t i = 0; i < h->scene.bodies.size(); ++i)
+	{
+		const b2Body* b = h->scene.bodies[i];
+		if (!b || !b->IsActive()) continue;
+		for (const b2Fixture* f = b->GetFixtureList(); f; f = f->GetNext())
+			for (int c = 0; c < f->GetShape()->GetChildCount(); ++c)
+			{
+				const int id = f->GetDeviceId() + c;
+				if (id >= cap) continue;
+				out2[2 * id] = (int)i;
+				out2[2 * id + 1] = FixtureIndexInBody(f);
+			}
+	}
+	return n;
+}
+
+// The Testbed's pick (Test.cpp:132, 168): b2World::QueryAABB over the point's zero-size box, then b2Fixture::TestPoint.
+// (body, fixture index in body) of every fixture kept, sorted; returns the count.
+int b2h_query_point(b2h_world* h, float x, float y, int cap, int* out)
+{
+	AllFixtures cb;
+	b2AABB aabb;
+	aabb.lowerBound.Set(x, y);
+	aabb.upperBound.Set(x, y);
+	h->world->QueryAABB(&cb, aabb);
+	std::vector<std::pair<int, int> > ids;
+	for (size_t i = 0; i < cb.hits.size(); ++i)
+		if (cb.hits[i]->TestPoint(b2Vec2(x, y))) ids.push_back(std::make_pair(h->bodyIndex[cb.hits[i]->GetBody()], FixtureIndexInBody(cb.hits[i])));
+	std::sort(ids.begin(), ids.end());
+	for (size_t i = 0; i < ids.size() && (int)i < cap; ++i)
+	{
+		out[2 * i] = ids[i].first;
+		out[2 * i + 1] = ids[i].second;
+	}
+	return (int)ids.size();
+}
+
+// Edits between steps through the drop-in API: op 0 creates a dynamic body with a 0.5 x 0.5 box at (x, y, angle) and
+// returns its row; op 1 destroys the newest fixture of body `body`; op 2 SetTransform(body, (x, y), angle); op 3
+// SetActive(body, false); op 4 sets the categoryBits of the body's newest fixture to x (SetFilterData); op 5 makes it a
+// sensor (x != 0) or not (SetSensor). Returns 0 (op 0: the new row), -1 for an op that does not apply.
+int b2h_edit(b2h_world* h, int op, int body, float x, float y, float angle)
+{
+	if (op == 0)
+	{
+		b2BodyDef bd;
+		bd.type = b2_dynamicBody;
+		bd.position.Set(x, y);
+		bd.angle = angle;
+		b2Body* b = h->world->CreateBody(&bd);
+		b2PolygonShape box;
+		box.SetAsBox(0.5f, 0.5f);
+		b->CreateFixture(&box, 1.0f);
+		h->scene.bodies.push_back(b);
+		h->bodyIndex[b] = (int)h->scene.bodies.size() - 1;
+		return (int)h->scene.bodies.size() - 1;
+	}
+	if (body < 0 || (size_t)body >= h->scene.bodies.size() || !h->scene.bodies[body]) return -1;
+	b2Body* b = h->scene.bodies[body];
+	if (op == 1)
+	{
+		if (!b->GetFixtureList()) return -1;
+		b->DestroyFixture(b->GetFixtureList());
+	}
+	else if (op == 2) b->SetTransform(b2Vec2(x, y), angle);
+	else if (op == 3) b->SetActive(false);
+	else if (op == 4 || op == 5)
+	{
+		b2Fixture* f = b->GetFixtureList();
+		if (!f) return -1;
+		if (op == 5) f->SetSensor(x != 0.0f);
+		else
+		{
+			b2Filter filter = f->GetFilterData();
+			filter.categoryBits = (uint16)(int)x;
+			f->SetFilterData(filter);
+		}
+	}
+	else return -1;
+	return 0;
+}
+
+// The host's filter data per device fixture id: out2[2 * id] = categoryBits, out2[2 * id + 1] = 1 for a sensor; -1 rows for
+// ids nobody owns. Returns the number of device fixture ids.
+int b2h_fixture_filters(b2h_world* h, int cap, int* out2)
+{
+	int n = 0;
+	for (size_t i = 0; i < h->scene.bodies.size(); ++i)
+		if (h->scene.bodies[i])
+			for (const b2Fixture* f = h->scene.bodies[i]->GetFixtureList(); f; f = f->GetNext())
+				n = std::max(n, (int)(f->GetDeviceId() + f->GetShape()->GetChildCount()));
+	for (int k = 0; k < std::min(n, cap); ++k) out2[2 * k] = out2[2 * k + 1] = -1;
+	for (size_t i = 0; i < h->scene.bodies.size(); ++i)
+	{
+		const b2Body* b = h->scene.bodies[i];
+		if (!b || !b->IsActive()) continue;
+		for (const b2Fixture* f = b->GetFixtureList(); f; f = f->GetNext())
+			for (int c = 0; c < f->GetShape()->GetChildCount(); ++c)
+			{
+				const int id = f->GetDeviceId() + c;
+				if (id >= cap) continue;
+				out2[2 * id] = (int)f->GetFilterData().categoryBits;
+				out2[2 * id + 1] = f->IsSensor() ? 1 : 0;
+			}
+	}
+	return n;
+}
+
+// b2World::RayCast with a closest-hit callback that skips (returns -1 for) the fixtures a b2hip_query_filter would not pass:
+// (categoryBits & mask) == 0, or a sensor while `sensors` is 0. out7 as b2h_raycast_closest; returns 1 on a hit.
+namespace
+{
+struct ClosestPassingHit : b2RayCastCallback
+{
+	const b2Fixture* fixture = nullptr;
+	b2Vec2 point, normal;
+	float32 fraction = 1.0f;
+	int mask = 0xFFFF, sensors = 1;
+	float32 ReportFixture(b2Fixture* f, const b2Vec2& p, const b2Vec2& n, float32 fr) override
+	{
+		if ((f->GetFilterData().categoryBits & mask) == 0 || (!sensors && f->IsSensor())) return -1.0f;
+		fixture = f; point = p; normal = n; fraction = fr;
+		return fr;
+	}
+};
+}
+int b2h_raycast_closest_filtered(b2h_world* h, float x1, float y1, float x2, float y2, int mask, int sensors, float* out7)
+{
+	ClosestPassingHit cb;
+	cb.mask = mask;
+	cb.sensors = sensors;
+	h->world->RayCast(&cb, b2Vec2(x1, y1), b2Vec2(x2, y2));
+	if (!cb.fixture) return 0;
+	out7[0] = (float)h->bodyIndex[cb.fixture->GetBody()];
+	out7[1] = (float)FixtureIndexInBody(cb.fixture);
+	out7[2] = cb.point.x; out7[3] = cb.point.y;
+	out7[4] = cb.normal.x; out7[5] = cb.normal.y;
+	out7[6] = cb.fraction;
+	return 1;
+}
+#endif
+
 // Dumps every contact of the world's contact list.
 //   ids:      4 ints  per contact: bodyA, fixtureA (index within body), bodyB, fixtureB
 //   flags:    1 int   per contact: bit0 touching, bit1 enabled

@@ -126,6 +126,14 @@ CONTACT_DTYPE = np.dtype([("fixture_a", "i4"), ("fixture_b", "i4"), ("body_a", "
                           ("normal_impulse", "f4", 2), ("tangent_impulse", "f4", 2), ("id_key", "u4", 2),
                           ("friction", "f4"), ("restitution", "f4"), ("tangent_speed", "f4")])
 
+class QueryFilter(C.Structure):
+    _fields_ = [("mask", C.c_uint16), ("include_sensors", C.c_int)]
+
+
+QUERY_ITEM_DTYPE = np.dtype([("fixture", "i4"), ("body", "i4")])
+RAY_HIT_DTYPE = np.dtype([("fixture", "i4"), ("body", "i4"), ("point", "f4", 2), ("normal", "f4", 2), ("fraction", "f4"),
+                          ("pad", "i4")])
+
 _lib = None
 
 
@@ -188,6 +196,9 @@ def _configure(L, optional_ok=False):
         "b2hip_fixture_set_sensor": [C.c_void_p, C.c_int, C.c_int],
         "b2hip_fixture_refilter": [C.c_void_p, C.c_int],
         "b2hip_set_lazy_readback": [C.c_void_p, C.c_int],
+        "b2hip_query_aabbs": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_query_points": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_ray_cast_closest": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_void_p],
     }
     for name, argtypes in sigs.items():
         try:
@@ -286,10 +297,19 @@ class World:
         self.p = p
         return self
 
+    @classmethod
+    def borrow(cls, ptr, library=None):
+        """A view of a world owned elsewhere (the drop-in's b2World::GetDeviceWorld()): close() leaves the world alone."""
+        self = cls.__new__(cls)
+        self.L = library if library is not None else lib()
+        self.p = C.c_void_p(ptr)
+        self._borrowed = True
+        return self
+
     def close(self):
-        if self.p:
+        if self.p and not getattr(self, "_borrowed", False):
             self.L.b2hip_world_destroy(self.p)
-            self.p = None
+        self.p = None
 
     def __del__(self):
         try:
@@ -524,6 +544,52 @@ class World:
         ms = (C.c_float * 13)()
         _check(self.L.b2hip_get_profile(self.p, ms))
         return list(ms)
+
+    # ---- batched queries on the device (include/b2hip.h: b2hip_query_aabbs, b2hip_query_points, b2hip_ray_cast_closest)
+    @staticmethod
+    def _pairs(a, name):
+        a = np.ascontiguousarray(a, np.float32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("%s: an (n, 2) array is expected, got shape %s" % (name, a.shape))
+        return a
+
+    def _query(self, fn, data, n, mask, sensors):
+        f = QueryFilter(mask, int(bool(sensors)))
+        offsets = np.zeros(n + 1, np.int32)
+        items = np.zeros(max(n, 1) * 8, QUERY_ITEM_DTYPE)
+        for _ in range(2):  # (once more with the exact capacity when the first guess was short)
+            total = _check(fn(self.p, n, data.ctypes.data_as(C.c_void_p), C.byref(f), items.size,
+                              offsets.ctypes.data_as(C.c_void_p), items.ctypes.data_as(C.c_void_p)))
+            if total <= items.size:
+                return offsets, items[:total]
+            items = np.zeros(total, QUERY_ITEM_DTYPE)
+        raise B2HipError("query: the result grew between two identical calls")
+
+    def query_aabbs(self, lower, upper, mask=0xFFFF, sensors=True):
+        """Every fixture whose fat AABB overlaps box i = (lower[i], upper[i]): returns (offsets[n + 1], items) with
+        items[offsets[i]:offsets[i + 1]] the (fixture, body) rows of box i in ascending fixture id."""
+        lo, hi = self._pairs(lower, "lower"), self._pairs(upper, "upper")
+        if lo.shape != hi.shape:
+            raise ValueError("query_aabbs: lower and upper differ in shape")
+        boxes = np.ascontiguousarray(np.concatenate([lo, hi], axis=1))
+        return self._query(self.L.b2hip_query_aabbs, boxes, len(boxes), mask, sensors)
+
+    def query_points(self, points, mask=0xFFFF, sensors=True):
+        """The fixtures whose shape contains point i (b2Fixture::TestPoint within the fat AABB): (offsets, items) as query_aabbs."""
+        pts = self._pairs(points, "points")
+        return self._query(self.L.b2hip_query_points, pts, len(pts), mask, sensors)
+
+    def ray_cast_closest(self, p1, p2, mask=0xFFFF, sensors=True):
+        """Closest hit of ray i from p1[i] to p2[i]: a RAY_HIT_DTYPE array, fixture = -1 where the ray hits nothing."""
+        a, b = self._pairs(p1, "p1"), self._pairs(p2, "p2")
+        if a.shape != b.shape:
+            raise ValueError("ray_cast_closest: p1 and p2 differ in shape")
+        rays = np.ascontiguousarray(np.concatenate([a, b], axis=1))
+        out = np.zeros(len(rays), RAY_HIT_DTYPE)
+        f = QueryFilter(mask, int(bool(sensors)))
+        _check(self.L.b2hip_ray_cast_closest(self.p, len(rays), rays.ctypes.data_as(C.c_void_p), C.byref(f),
+                                             out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def solver_timing(self):
         ms, by, ct, b = C.c_float(), C.c_double(), C.c_int(), C.c_int()

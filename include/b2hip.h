@@ -724,6 +724,59 @@ int b2hip_set_kernel_timing(b2hip_world* w, int enable);
 int b2hip_set_kernel_timing_units(b2hip_world* w, long long units_a, long long units_b);
 int b2hip_get_kernel_timing(b2hip_world* w, char* name, int name_cap, float* total_ms, int* launches, double* algorithmic_bytes);
 
+/* ---- Batched world queries on the device (csrc/b2hip_api_query.h, csrc/b2d_kernels_query.h) ------------------------------
+ * Many AABB, point or closest-ray queries in one blocking call, answered from the world's device state between steps:
+ * every query sees the world that b2hip_get_fat_aabbs / b2hip_get_body_states report at the moment of the call (edits made
+ * since the last step are uploaded first, as the next step would upload them; a world that is queried steps bit for bit
+ * like one that is not). b2World::QueryAABB / RayCast keep their host path; these are for batches (sensor sweeps, lidar).
+ *
+ * filter: a fixture is a candidate when (category_bits & mask) != 0 and (include_sensors || !is_sensor). NULL means
+ *   {0xFFFF, 1}: exactly the fixtures b2World::QueryAABB / RayCast consider.
+ * fixture ids are device fixture ids (b2Fixture::GetDeviceId() + child index for a chain); body ids are device body ids.
+ *
+ * b2hip_query_aabbs: boxes = 4n floats (lower.x, lower.y, upper.x, upper.y). Reports every live proxy whose fat AABB
+ *   overlaps the box, touching included (b2TestOverlap, the set b2World::QueryAABB reports), once, in ascending fixture
+ *   id. A box with lower > upper or a NaN coordinate reports nothing.
+ * b2hip_query_points: points = 2n floats. Reports the proxies whose fat AABB contains the point and whose shape contains it
+ *   at the body's transform (b2Fixture::TestPoint; edges and chains contain no point), in ascending fixture id.
+ * Both: offsets[n + 1] (offsets[i] .. offsets[i + 1] are query i's items, offsets[n] the total) are always complete;
+ *   items receives the first min(total, cap) entries. Returns the total (>= 0) or a b2hip_status: when it exceeds cap,
+ *   call again with cap = the total.
+ * b2hip_ray_cast_closest: rays = 4n floats (p1.x, p1.y, p2.x, p2.y). out[i] is the hit that b2World::RayCast reports last
+ *   to a callback returning the reported fraction: fraction and normal from the shape's ray cast, point = (1 - fraction)
+ *   * p1 + fraction * p2. A miss, a zero-length ray or a NaN coordinate gives fixture = body = -1. Where two fixtures are
+ *   hit at the same fraction the LOWEST fixture id is reported (the reference keeps the one its tree visits last).
+ *   Returns B2HIP_OK or a b2hip_status.
+ * Cost: a box, point or ray is answered from the cells of the broad-phase grid it can reach. A box window of more than
+ *   4096 grid cells, a ray longer than 4096 cells, or a coordinate beyond 1e8 in magnitude tests every proxy of the world
+ *   from one wave instead (10^6 candidates per query on a 10^6-body world). A box or point query with more than 4096 items
+ *   is put in order by two extra launches, one after the other from the host, the second one workgroup reading a flag
+ *   per proxy of the world.
+ * All three: n <= 2^24 (more: B2HIP_ERR_INVALID); inside an open step B2HIP_ERR_INVALID; on a sharded world
+ *   (b2hip_set_shard with more than one rank, b2hip_shard_spatial) B2HIP_ERR_UNSUPPORTED. Results are the same bytes run
+ *   after run. The call runs on the world's stream and returns when the results are on the host. */
+typedef struct b2hip_query_filter
+{
+	uint16_t mask;
+	int include_sensors;
+} b2hip_query_filter;
+typedef struct b2hip_query_item
+{
+	int32_t fixture, body;
+} b2hip_query_item;
+typedef struct b2hip_ray_hit
+{
+	int32_t fixture, body;
+	float point_x, point_y, normal_x, normal_y, fraction;
+	int32_t pad;
+} b2hip_ray_hit;
+#define B2HIP_QUERY_MAX (1 << 24)
+int b2hip_query_aabbs(b2hip_world* w, int n, const float* boxes4n, const b2hip_query_filter* f, int cap, int32_t* offsets,
+                      b2hip_query_item* items);
+int b2hip_query_points(b2hip_world* w, int n, const float* points2n, const b2hip_query_filter* f, int cap, int32_t* offsets,
+                       b2hip_query_item* items);
+int b2hip_ray_cast_closest(b2hip_world* w, int n, const float* rays4n, const b2hip_query_filter* f, b2hip_ray_hit* out);
+
 #ifdef __cplusplus
 }
 #endif
