@@ -1,4 +1,5 @@
-// b2d_kernels_query.h - batched world queries between steps (b2hip_query_aabbs / b2hip_query_points / b2hip_ray_cast_closest).
+// b2d_kernels_query.h - batched world queries between steps (b2hip_query_aabbs / b2hip_query_points / b2hip_ray_cast_closest /
+// b2hip_query_shapes / b2hip_shape_cast_closest).
 //
 // Everything is read from the world's device state: the fat AABBs, the proxies' filters and shapes, the bodies' transforms,
 // and the hashed grid of b2d_kernels_broadphase.h, rebuilt from every proxy's box just before (gridRebuildNow). One WAVE per
@@ -7,14 +8,15 @@
 // the same bucket would show a proxy twice; a candidate counts only in the cell its own centre lies in (the bucket dedup).
 // Proxies wider than the limit (DW::largeProxies) are tested by every query.
 //
-// Determinism: the grid's order inside a bucket depends on arrival, so nothing here depends on it. Box and point queries
-// sort each query's items by fixture id (k_query_sort, k_query_compact_big); rays keep the smallest (fraction bits, fixture)
-// key, a total order.
+// Determinism: the grid's order inside a bucket depends on arrival, so nothing here depends on it. Box, point and shape
+// queries sort each query's items by fixture id (k_query_sort, k_query_compact_big); rays and shape casts keep the smallest
+// (fraction bits, fixture) key, a total order.
 #ifndef B2D_KERNELS_QUERY_H
 #define B2D_KERNELS_QUERY_H
 
 #include "b2d_kernels_broadphase.h"
 #include "b2d_kernels_collide.h"
+#include "b2d_shapecast.h"
 #include "b2d_shape_geom.h"
 
 #define QUERY_WINDOW_MAX 4096     // cells a window may have; a wider one scans every proxy
@@ -119,18 +121,58 @@ __device__ __forceinline__ void queryVisitAll(const DW& W, int lane, F& visit)
 	}
 }
 
-// Box and point queries. pass 0: counts[i] = items of query i; pass 1: query i's items (fixture ids, unsorted) at
-// items[offsets[i] ...]. points: boxes[i] = (x, y, x, y) and the shape must contain the point (b2dShapeTestPoint).
-template <int PASS, bool POINTS>
-__device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, int n, uint32_t mask, int sensors, int* counts,
-                                               const int* offsets, int* items)
+// The record of one shape query or shape cast (b2hip_query_shapes / b2hip_shape_cast_closest): the pose as a transform the
+// host built (sinf / cosf there, as b2Rot::Set), the index of the query shape in the call's table, the cast's translation.
+struct QueryPose
+{
+	float x, y, c, s;
+	float tx, ty;
+	int32_t shape, pad;
+};
+
+#define QUERY_BOX 0
+#define QUERY_POINT 1
+#define QUERY_SHAPE 2
+
+__device__ __forceinline__ Xf queryPoseXf(const QueryPose& qp)
+{
+	Xf xf;
+	xf.p = v2(qp.x, qp.y);
+	xf.q.s = qp.s;
+	xf.q.c = qp.c;
+	return xf;
+}
+
+// Box, point and shape queries. pass 0: counts[i] = items of query i; pass 1: query i's items (fixture ids, unsorted) at
+// items[offsets[i] ...]. QUERY_POINT: boxes[i] = (x, y, x, y) and the shape must contain the point (b2dShapeTestPoint).
+// QUERY_SHAPE: the box is the query shape's AABB at its pose (b2Shape::ComputeAABB), computed by every lane from the
+// table, and a candidate must overlap the shape (b2TestOverlap: GJK distance with radii from a zeroed cache below
+// 10 epsilon; the query shape is proxy A, as in b2TestOverlap(query, 0, fixture, child, xfQ, xfBody)). Both proxies point
+// into global memory (W.shapes, the query table), so b2dSupport's run-time indexing stays out of scratch.
+template <int PASS, int KIND>
+__device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, const QueryPose* poses, const ShapeRec* qshapes, int n,
+                                               uint32_t mask, int sensors, int* counts, const int* offsets, int* items)
 {
 	const int lane = (int)(threadIdx.x & 63u);
 	const int nWaves = (int)((gridDim.x * blockDim.x) >> 6);
 	for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nWaves)
 	{
-		const float4 b = boxes[i];
-		if (!(b.x <= b.z && b.y <= b.w)) // (lower > upper, or a NaN: nothing)
+		float4 b;
+		Xf xfQ;
+		GjkProxy pQ;
+		bool nan = false;
+		if (KIND == QUERY_SHAPE)
+		{
+			const QueryPose qp = poses[i];
+			nan = isnan(qp.x) || isnan(qp.y) || isnan(qp.c) || isnan(qp.s);
+			xfQ = queryPoseXf(qp);
+			const ShapeRec* rec = qshapes + qp.shape;
+			pQ = b2dProxy(rec);
+			const AABB qa = b2dShapeAABB(rec, xfQ);
+			b = make_float4(qa.lo.x, qa.lo.y, qa.hi.x, qa.hi.y);
+		}
+		else b = boxes[i];
+		if (nan || !(b.x <= b.z && b.y <= b.w)) // (lower > upper, or a NaN: nothing)
 		{
 			if (PASS == 0 && lane == 0) counts[i] = 0;
 			continue;
@@ -149,7 +191,17 @@ __device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, int n,
 				f.lo = v2(fat.x, fat.y);
 				f.hi = v2(fat.z, fat.w);
 				hit = b2dAabbOverlap(a, f) && queryFilterPasses(W, q, mask, sensors);
-				if (POINTS && hit) hit = b2dShapeTestPoint(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), a.lo);
+				if (KIND == QUERY_POINT && hit) hit = b2dShapeTestPoint(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), a.lo);
+				if (KIND == QUERY_SHAPE && hit)
+				{
+					GjkCache cache;
+					cache.count = 0;
+					cache.metric = 0.0f;
+					for (int k = 0; k < 3; ++k) cache.indexA[k] = cache.indexB[k] = 0;
+					GjkOutput dist;
+					b2dDistance(dist, cache, pQ, xfQ, b2dProxy(W.shapes + W.p_shape[q]), loadXf(W.b_xf, W.p_body[q]), true);
+					hit = dist.distance < 10.0f * B2D_EPSILON;
+				}
 			}
 			const unsigned long long m = __ballot(hit);
 			if (PASS == 1 && hit)
@@ -167,19 +219,29 @@ __device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, int n,
 
 __global__ __launch_bounds__(256) void k_query_aabbs_count(DW W, const float4* boxes, int n, uint32_t mask, int sensors, int* counts)
 {
-	queryBoxesWave<0, false>(W, boxes, n, mask, sensors, counts, nullptr, nullptr);
+	queryBoxesWave<0, QUERY_BOX>(W, boxes, nullptr, nullptr, n, mask, sensors, counts, nullptr, nullptr);
 }
 __global__ __launch_bounds__(256) void k_query_aabbs_fill(DW W, const float4* boxes, int n, uint32_t mask, int sensors, const int* offsets, int* items)
 {
-	queryBoxesWave<1, false>(W, boxes, n, mask, sensors, nullptr, offsets, items);
+	queryBoxesWave<1, QUERY_BOX>(W, boxes, nullptr, nullptr, n, mask, sensors, nullptr, offsets, items);
 }
 __global__ __launch_bounds__(256) void k_query_points_count(DW W, const float4* boxes, int n, uint32_t mask, int sensors, int* counts)
 {
-	queryBoxesWave<0, true>(W, boxes, n, mask, sensors, counts, nullptr, nullptr);
+	queryBoxesWave<0, QUERY_POINT>(W, boxes, nullptr, nullptr, n, mask, sensors, counts, nullptr, nullptr);
 }
 __global__ __launch_bounds__(256) void k_query_points_fill(DW W, const float4* boxes, int n, uint32_t mask, int sensors, const int* offsets, int* items)
 {
-	queryBoxesWave<1, true>(W, boxes, n, mask, sensors, nullptr, offsets, items);
+	queryBoxesWave<1, QUERY_POINT>(W, boxes, nullptr, nullptr, n, mask, sensors, nullptr, offsets, items);
+}
+__global__ __launch_bounds__(256) void k_query_shapes_count(DW W, const QueryPose* poses, const ShapeRec* qshapes, int n, uint32_t mask,
+                                                            int sensors, int* counts)
+{
+	queryBoxesWave<0, QUERY_SHAPE>(W, nullptr, poses, qshapes, n, mask, sensors, counts, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void k_query_shapes_fill(DW W, const QueryPose* poses, const ShapeRec* qshapes, int n, uint32_t mask,
+                                                           int sensors, const int* offsets, int* items)
+{
+	queryBoxesWave<1, QUERY_SHAPE>(W, nullptr, poses, qshapes, n, mask, sensors, nullptr, offsets, items);
 }
 
 // One workgroup per query: its items sorted ascending in LDS (bitonic network over the next power of two, padded with
@@ -370,6 +432,112 @@ __global__ __launch_bounds__(256) void k_query_rays(DW W, const float4* rays, in
 				o.normal_x = hit.normal.x;
 				o.normal_y = hit.normal.y;
 				o.fraction = f;
+			}
+			out[i] = o;
+		}
+	}
+}
+
+// Closest shape cast, one WAVE per cast (b2hip_shape_cast_closest), walked as k_query_rays walks a ray. The sweep box is the
+// union of the query shape's AABB at the pose and at the pose moved by the translation; a candidate is a live proxy passing
+// the filter whose fat AABB overlaps the WHOLE sweep box, whichever cells it was found in, so the answer does not depend on
+// the walk. Its hit is b2ShapeCast with the fixture's child at its body's transform as proxy A, the query shape at the
+// pose as proxy B and the translation as B's (the Testbed's ShapeCast.h); best = the smallest (lambda bits, fixture id).
+// The walk: large proxies first; then the sweep box's window once when it has at most QUERY_WINDOW_MAX cells; else the
+// translation in cell-long pieces, piece k's box being the shape's box swept over [t0, t1] grown by `margin`, stopping once
+// the best lambda is below t1; else (too many pieces, or a coordinate beyond QUERY_COORD_MAX) every proxy of the world.
+// The margin: b2ShapeCast reports a hit once the cores are within sigma + tolerance, sigma = the two skins less
+// b2_polygonRadius, a skin being the shape's radius or b2_polygonRadius if that is larger. The query box holds the query
+// shape's radius and a fixture's fat box its own (none for a chain link) plus b2_aabbExtension, so the cores' reach beyond
+// the tight boxes is at most 2 b2_polygonRadius + tolerance - both skins at b2_polygonRadius over a zero radius - taken
+// here on top of a rounding term that grows with the coordinates' magnitude.
+__global__ __launch_bounds__(256) void k_query_shape_casts(DW W, const QueryPose* casts, const ShapeRec* qshapes, int n, uint32_t mask,
+                                                           int sensors, b2hip_ray_hit* out)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const int nWaves = (int)((gridDim.x * blockDim.x) >> 6);
+	for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nWaves)
+	{
+		const QueryPose qp = casts[i];
+		const ShapeRec* rec = qshapes + qp.shape;
+		const GjkProxy pB = b2dProxy(rec);
+		const Xf xfB = queryPoseXf(qp);
+		const V2 t = v2(qp.tx, qp.ty);
+		unsigned long long best = ~0ull;
+		const bool finite = isfinite(qp.x) && isfinite(qp.y) && isfinite(qp.c) && isfinite(qp.s) && isfinite(qp.tx) && isfinite(qp.ty);
+		if (finite)
+		{
+			Xf xfEnd = xfB;
+			xfEnd.p = xfB.p + t;
+			const AABB box0 = b2dShapeAABB(rec, xfB);
+			const AABB sweep = b2dAabbCombine(box0, b2dShapeAABB(rec, xfEnd));
+			const float mag = fmaxf(fmaxf(fabsf(sweep.lo.x), fabsf(sweep.lo.y)), fmaxf(fabsf(sweep.hi.x), fabsf(sweep.hi.y)));
+			const float margin = 1.0e-3f + 1.0e-5f * mag + 2.0f * B2D_POLYGON_RADIUS + 0.5f * B2D_LINEAR_SLOP;
+			auto visit = [&](bool valid, int q, float4 fat)
+			{
+				bool cand = valid && !(fat.x > sweep.hi.x || fat.y > sweep.hi.y || sweep.lo.x > fat.z || sweep.lo.y > fat.w);
+				if (cand) cand = queryFilterPasses(W, q, mask, sensors);
+				if (cand)
+				{
+					ShapeCastResult r;
+					if (b2dShapeCast(&r, b2dProxy(W.shapes + W.p_shape[q]), loadXf(W.b_xf, W.p_body[q]), pB, xfB, t))
+					{
+						const unsigned long long key = ((unsigned long long)__float_as_uint(r.lambda + 0.0f) << 32) | (uint32_t)q;
+						best = key < best ? key : best;
+					}
+				}
+			};
+			queryVisitLarge(W, lane, visit);
+			bool all = !(mag <= QUERY_COORD_MAX);
+			const float4 whole = make_float4(sweep.lo.x, sweep.lo.y, sweep.hi.x, sweep.hi.y);
+			if (!all && !queryVisitGrid(W, lane, whole, visit))
+			{
+				const float len = sqrtf(t.x * t.x + t.y * t.y);
+				const float pieces = ceilf(len / gridCell(W));
+				all = !(pieces <= (float)QUERY_WINDOW_MAX);
+				if (!all)
+				{
+					const int np = pieces < 1.0f ? 1 : (int)pieces;
+					for (int k = 0; k < np; ++k)
+					{
+						const float t0 = (float)k / (float)np, t1 = k + 1 == np ? 1.0f : (float)(k + 1) / (float)np;
+						const V2 a = t0 * t, b = t1 * t;
+						const float4 box = make_float4(box0.lo.x + fminf(a.x, b.x) - margin, box0.lo.y + fminf(a.y, b.y) - margin,
+						                               box0.hi.x + fmaxf(a.x, b.x) + margin, box0.hi.y + fmaxf(a.y, b.y) + margin);
+						if (!queryVisitGrid(W, lane, box, visit))
+						{
+							all = true;
+							break;
+						}
+						best = waveMinU64(best);
+						if (best != ~0ull && __uint_as_float((uint32_t)(best >> 32)) < t1) break;
+					}
+				}
+			}
+			if (all) queryVisitAll(W, lane, visit);
+			best = waveMinU64(best);
+		}
+		if (lane == 0)
+		{
+			b2hip_ray_hit o;
+			o.fixture = -1;
+			o.body = -1;
+			o.point_x = o.point_y = o.normal_x = o.normal_y = 0.0f;
+			o.fraction = 1.0f;
+			o.pad = 0;
+			if (best != ~0ull)
+			{
+				const int q = (int)(uint32_t)best;
+				const int body = W.p_body[q];
+				ShapeCastResult r;
+				(void)b2dShapeCast(&r, b2dProxy(W.shapes + W.p_shape[q]), loadXf(W.b_xf, body), pB, xfB, t); // (the kept hit again)
+				o.fixture = q;
+				o.body = body;
+				o.point_x = r.point.x;
+				o.point_y = r.point.y;
+				o.normal_x = r.normal.x;
+				o.normal_y = r.normal.y;
+				o.fraction = r.lambda;
 			}
 			out[i] = o;
 		}

@@ -233,7 +233,7 @@ void b2hip_world_destroy(b2hip_world* w)
 	w->pairFirst.release(); w->pairRank.release(); w->scanTmp.release(); w->radixHist.release(); w->radixHistScan.release();
 	w->keepFlag.release(); w->keepScan.release(); w->scanTmp4.release(); w->scanFlags.release(); w->stateOut.release(); w->consts.release();
 	w->qIn.release(); w->qCounts.release(); w->qOffsets.release(); w->qItems.release(); w->qFlags.release(); w->qScanWork.release();
-	w->qScanWords.release(); w->qWords.release(); w->qHits.release();
+	w->qScanWords.release(); w->qWords.release(); w->qHits.release(); w->qPoses.release(); w->qShapes.release();
 	if (w->qPinned) (void)hipHostFree(w->qPinned);
 	if (w->h_state) (void)hipHostFree(w->h_state);
 	if (w->h_dstate) (void)hipHostFree(w->h_dstate);
@@ -327,28 +327,36 @@ int b2hip_create_body(b2hip_world* w, const b2hip_body_def* def)
 	return (int)w->bodies.size() - 1;
 }
 
+// The device record of a b2hip_shape (b2hip_create_fixture, and the query shapes of b2hip_query_shapes /
+// b2hip_shape_cast_closest): nullptr, or why the shape is refused.
+static const char* shapeRecordOf(const b2hip_shape* shape, ShapeRec* rec)
+{
+	if (shape->type != B2HIP_SHAPE_CIRCLE && shape->type != B2HIP_SHAPE_EDGE && shape->type != B2HIP_SHAPE_POLYGON && shape->type != B2HIP_SHAPE_CHAIN)
+	{
+		return "unknown shape type";
+	}
+	memset(rec, 0, sizeof(*rec));
+	rec->type = shape->type;
+	rec->count = shape->count;
+	rec->radius = shape->radius;
+	rec->centroid = v2(shape->centroid[0], shape->centroid[1]);
+	int nv = shape->type == B2HIP_SHAPE_POLYGON ? shape->count : (B2D_IS_SEGMENT(shape->type) ? 4 : 1);
+	if (nv > B2D_MAX_POLY_VERTS) return "too many polygon vertices";
+	for (int i = 0; i < nv; ++i)
+	{
+		rec->verts[i] = v2(shape->verts[2 * i], shape->verts[2 * i + 1]);
+		if (shape->type == B2HIP_SHAPE_POLYGON) rec->normals[i] = v2(shape->normals[2 * i], shape->normals[2 * i + 1]);
+	}
+	return nullptr;
+}
+
 int b2hip_create_fixture(b2hip_world* w, int body, const b2hip_fixture_def* def, const b2hip_shape* shape)
 {
 	if (!w || !def || !shape) return setError(B2HIP_ERR_INVALID, "null argument");
 	if (int rcu = checkUsable(w, "b2hip_create_fixture", true)) return rcu;
 	if (body < 0 || body >= (int)w->bodies.size()) return setError(B2HIP_ERR_INVALID, "bad body id");
-	if (shape->type != B2HIP_SHAPE_CIRCLE && shape->type != B2HIP_SHAPE_EDGE && shape->type != B2HIP_SHAPE_POLYGON && shape->type != B2HIP_SHAPE_CHAIN)
-	{
-		return setError(B2HIP_ERR_INVALID, "unknown shape type");
-	}
 	ShapeRec rec;
-	memset(&rec, 0, sizeof(rec));
-	rec.type = shape->type;
-	rec.count = shape->count;
-	rec.radius = shape->radius;
-	rec.centroid = v2(shape->centroid[0], shape->centroid[1]);
-	int nv = shape->type == B2HIP_SHAPE_POLYGON ? shape->count : (B2D_IS_SEGMENT(shape->type) ? 4 : 1);
-	if (nv > B2D_MAX_POLY_VERTS) return setError(B2HIP_ERR_INVALID, "too many polygon vertices");
-	for (int i = 0; i < nv; ++i)
-	{
-		rec.verts[i] = v2(shape->verts[2 * i], shape->verts[2 * i + 1]);
-		if (shape->type == B2HIP_SHAPE_POLYGON) rec.normals[i] = v2(shape->normals[2 * i], shape->normals[2 * i + 1]);
-	}
+	if (const char* why = shapeRecordOf(shape, &rec)) return setError(B2HIP_ERR_INVALID, why);
 	markDirty(w, body);
 	HostBody& b = w->bodies[body];
 	HostFixture f;

@@ -197,6 +197,8 @@ struct b2hip_world
 	DevArray<float4> qIn;
 	DevArray<int> qCounts, qOffsets, qItems, qFlags, qScanWork, qScanWords, qWords;
 	DevArray<b2hip_ray_hit> qHits;
+	DevArray<QueryPose> qPoses; // shape queries and casts: pose, shape index, translation per query
+	DevArray<ShapeRec> qShapes; // ... and the call's query shapes (the GJK proxies point into this table)
 	ScanFlags qScan;
 	void* qPinned = nullptr;
 	size_t qPinnedBytes = 0;

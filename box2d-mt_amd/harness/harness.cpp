@@ -6,9 +6,13 @@
 // The harness pattern follows the reference's own batch runner (Testbed/Framework/TestMT.cpp:50-132):
 // build a scene, step it with a b2ThreadPoolTaskExecutor, read back every body in creation order.
 #include "scenes.h"
+#if defined(B2H_BACKEND_AMD)
+#include "b2hip.h" // (b2hip_shape: the query shapes of b2h_query_shape / b2h_shape_cast_all)
+#endif
 
 #include <stdio.h>
 #include <string.h>
+#include <cmath>
 #include <map>
 #include <algorithm>
 
@@ -610,6 +614,164 @@ int b2h_raycast_closest_filtered(b2h_world* h, float x1, float y1, float x2, flo
 	out7[4] = cb.normal.x; out7[5] = cb.normal.y;
 	out7[6] = cb.fraction;
 	return 1;
+}
+
+// The query shape of b2hip_query_shapes / b2hip_shape_cast_closest as the drop-in's b2Shape, built from the record's raw
+// members (no Set / SetAsBox: the host and the device start from the same bits): ComputeAABB gives its box, and
+// b2DistanceProxy::Set(vertices, count, radius) its proxy.
+namespace
+{
+struct QueryShape
+{
+	b2CircleShape circle;
+	b2EdgeShape edge;
+	b2PolygonShape polygon;
+	b2ChainShape chain;
+	const b2Shape* shape = nullptr;
+	b2Vec2 verts[b2_maxPolygonVertices];
+	b2DistanceProxy proxy;
+	explicit QueryShape(const b2hip_shape& s)
+	{
+		for (int k = 0; k < b2_maxPolygonVertices; ++k) verts[k].Set(s.verts[2 * k], s.verts[2 * k + 1]);
+		int count = 1;
+		if (s.type == B2HIP_SHAPE_CIRCLE)
+		{
+			circle.m_p = verts[0];
+			circle.m_radius = s.radius;
+			shape = &circle;
+		}
+		else if (s.type == B2HIP_SHAPE_EDGE)
+		{
+			edge.m_vertex1 = verts[0];
+			edge.m_vertex2 = verts[1];
+			edge.m_vertex0 = verts[2];
+			edge.m_vertex3 = verts[3];
+			edge.m_hasVertex0 = (s.count & 1) != 0;
+			edge.m_hasVertex3 = (s.count & 2) != 0;
+			edge.m_radius = s.radius;
+			shape = &edge;
+			count = 2;
+		}
+		else if (s.type == B2HIP_SHAPE_CHAIN)
+		{
+			chain.CreateChain(verts, 2); // (one link: child 0)
+			chain.m_radius = s.radius;
+			shape = &chain;
+			count = 2;
+		}
+		else
+		{
+			polygon.m_count = s.count;
+			for (int k = 0; k < s.count; ++k)
+			{
+				polygon.m_vertices[k] = verts[k];
+				polygon.m_normals[k].Set(s.normals[2 * k], s.normals[2 * k + 1]);
+			}
+			polygon.m_centroid.Set(s.centroid[0], s.centroid[1]);
+			polygon.m_radius = s.radius;
+			shape = &polygon;
+			count = s.count;
+		}
+		proxy.Set(verts, count, s.radius);
+	}
+};
+
+// (device fixture id, child) of every proxy b2World::QueryAABB reports over `box`: a chain's fixture comes once per child
+// without the child index, so its children are those whose own fat AABB overlaps the box
+void proxiesOver(b2h_world* h, const b2AABB& box, std::vector<std::pair<const b2Fixture*, int> >& out)
+{
+	AllFixtures cb;
+	h->world->QueryAABB(&cb, box);
+	std::vector<const b2Fixture*> fs(cb.hits.begin(), cb.hits.end());
+	std::sort(fs.begin(), fs.end(), [](const b2Fixture* a, const b2Fixture* b) { return a->GetDeviceId() < b->GetDeviceId(); });
+	fs.erase(std::unique(fs.begin(), fs.end()), fs.end());
+	out.clear();
+	for (const b2Fixture* f : fs)
+	{
+		if (f->GetShape()->GetType() != b2Shape::e_chain) out.push_back(std::make_pair(f, 0));
+		else
+			for (int c = 0; c < f->GetShape()->GetChildCount(); ++c)
+				if (b2TestOverlap(f->GetAABB(c), box)) out.push_back(std::make_pair(f, c));
+	}
+}
+}
+
+// b2hip_query_shapes composed from the drop-in: b2World::QueryAABB over the query shape's box at (x, y, angle), then
+// b2TestOverlap(query shape, 0, fixture shape, child, xfQ, body transform) for each reported proxy. The device fixture ids
+// of those that overlap, ascending, in out (up to cap); returns their count.
+int b2h_query_shape(b2h_world* h, const b2hip_shape* s, float x, float y, float angle, int cap, int* out)
+{
+	if (x != x || y != y || angle != angle) return 0;
+	QueryShape q(*s);
+	b2Transform xf;
+	xf.Set(b2Vec2(x, y), angle);
+	b2AABB box;
+	q.shape->ComputeAABB(&box, xf, 0);
+	std::vector<std::pair<const b2Fixture*, int> > proxies;
+	proxiesOver(h, box, proxies);
+	std::vector<int> ids;
+	for (const auto& pc : proxies)
+	{
+		b2DistanceInput in;
+		in.proxyA = q.proxy;
+		in.proxyB.Set(pc.first->GetShape(), pc.second);
+		in.transformA = xf;
+		in.transformB = pc.first->GetBody()->GetTransform();
+		in.useRadii = true;
+		b2SimplexCache cache;
+		memset(&cache, 0, sizeof(cache));
+		b2DistanceOutput o;
+		b2Distance(&o, &cache, &in);
+		if (o.distance < 10.0f * b2_epsilon) ids.push_back(pc.first->GetDeviceId() + pc.second);
+	}
+	std::sort(ids.begin(), ids.end());
+	for (size_t i = 0; i < ids.size() && (int)i < cap; ++i) out[i] = ids[i];
+	return (int)ids.size();
+}
+
+// b2hip_shape_cast_closest composed from the drop-in: b2World::QueryAABB over the sweep box (the shape's box at the pose and
+// at the pose moved by (tx, ty)), then b2ShapeCast for each reported proxy with proxyA = the fixture's child at its body's
+// transform, proxyB = the query shape at the pose, translationB = (tx, ty). EVERY hit: ids2[2 k] its device fixture id,
+// ids2[2 k + 1] its device body id, out5[5 k] (lambda, point.x, point.y, normal.x, normal.y); returns the number of hits (up to
+// cap written).
+int b2h_shape_cast_all(b2h_world* h, const b2hip_shape* s, float x, float y, float angle, float tx, float ty, int cap, int* ids2,
+                       float* out5)
+{
+	if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(angle) || !std::isfinite(tx) || !std::isfinite(ty)) return 0;
+	QueryShape q(*s);
+	b2Transform xf;
+	xf.Set(b2Vec2(x, y), angle);
+	b2Transform xfEnd = xf;
+	xfEnd.p = xf.p + b2Vec2(tx, ty);
+	b2AABB a, b, box;
+	q.shape->ComputeAABB(&a, xf, 0);
+	q.shape->ComputeAABB(&b, xfEnd, 0);
+	box.Combine(a, b);
+	std::vector<std::pair<const b2Fixture*, int> > proxies;
+	proxiesOver(h, box, proxies);
+	int n = 0;
+	for (const auto& pc : proxies)
+	{
+		b2ShapeCastInput in;
+		in.proxyA.Set(pc.first->GetShape(), pc.second);
+		in.proxyB = q.proxy;
+		in.transformA = pc.first->GetBody()->GetTransform();
+		in.transformB = xf;
+		in.translationB.Set(tx, ty);
+		b2ShapeCastOutput o;
+		if (!b2ShapeCast(&o, &in)) continue;
+		if (n < cap)
+		{
+			ids2[2 * n] = pc.first->GetDeviceId() + pc.second;
+			ids2[2 * n + 1] = pc.first->GetBody()->GetDeviceId();
+			float* r = out5 + 5 * n;
+			r[0] = o.lambda;
+			r[1] = o.point.x; r[2] = o.point.y;
+			r[3] = o.normal.x; r[4] = o.normal.y;
+		}
+		++n;
+	}
+	return n;
 }
 #endif
 

@@ -133,6 +133,9 @@ class QueryFilter(C.Structure):
 QUERY_ITEM_DTYPE = np.dtype([("fixture", "i4"), ("body", "i4")])
 RAY_HIT_DTYPE = np.dtype([("fixture", "i4"), ("body", "i4"), ("point", "f4", 2), ("normal", "f4", 2), ("fraction", "f4"),
                           ("pad", "i4")])
+SHAPE_QUERY_DTYPE = np.dtype([("shape", "i4"), ("x", "f4"), ("y", "f4"), ("angle", "f4")])
+SHAPE_CAST_DTYPE = np.dtype([("shape", "i4"), ("x", "f4"), ("y", "f4"), ("angle", "f4"), ("tx", "f4"), ("ty", "f4"),
+                             ("pad", "i4", 2)])
 
 _lib = None
 
@@ -199,6 +202,10 @@ def _configure(L, optional_ok=False):
         "b2hip_query_aabbs": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_query_points": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_ray_cast_closest": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_void_p],
+        "b2hip_query_shapes": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int,
+                               C.c_void_p, C.c_void_p],
+        "b2hip_shape_cast_closest": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter),
+                                     C.c_void_p],
     }
     for name, argtypes in sigs.items():
         try:
@@ -553,12 +560,12 @@ class World:
             raise ValueError("%s: an (n, 2) array is expected, got shape %s" % (name, a.shape))
         return a
 
-    def _query(self, fn, data, n, mask, sensors):
+    def _query(self, fn, data, n, mask, sensors, lead=()):
         f = QueryFilter(mask, int(bool(sensors)))
         offsets = np.zeros(n + 1, np.int32)
         items = np.zeros(max(n, 1) * 8, QUERY_ITEM_DTYPE)
         for _ in range(2):  # (once more with the exact capacity when the first guess was short)
-            total = _check(fn(self.p, n, data.ctypes.data_as(C.c_void_p), C.byref(f), items.size,
+            total = _check(fn(self.p, *lead, n, data.ctypes.data_as(C.c_void_p), C.byref(f), items.size,
                               offsets.ctypes.data_as(C.c_void_p), items.ctypes.data_as(C.c_void_p)))
             if total <= items.size:
                 return offsets, items[:total]
@@ -589,6 +596,57 @@ class World:
         f = QueryFilter(mask, int(bool(sensors)))
         _check(self.L.b2hip_ray_cast_closest(self.p, len(rays), rays.ctypes.data_as(C.c_void_p), C.byref(f),
                                              out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    @staticmethod
+    def _shape_table(shapes, n, shape_index):
+        """(Shape array, shape count, int32 index per query): one Shape serves every query, n Shapes default to one each"""
+        one = isinstance(shapes, Shape)
+        shapes = [shapes] if one else list(shapes)
+        table = (Shape * max(len(shapes), 1))(*shapes)
+        if shape_index is None:
+            if not one and len(shapes) != n:
+                raise ValueError("shape_index is needed when the number of shapes (%d) is not the number of queries (%d)"
+                                 % (len(shapes), n))
+            shape_index = np.zeros(n, np.int32) if one else np.arange(n, dtype=np.int32)
+        shape_index = np.asarray(shape_index, np.int32).reshape(-1)
+        if len(shape_index) != n:
+            raise ValueError("shape_index: %d entries for %d queries" % (len(shape_index), n))
+        return table, len(shapes), shape_index
+
+    @staticmethod
+    def _poses(poses):
+        p = np.ascontiguousarray(poses, np.float32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("poses: an (n, 3) array of (x, y, angle) is expected, got shape %s" % (p.shape,))
+        return p
+
+    def query_shapes(self, shapes, poses, shape_index=None, mask=0xFFFF, sensors=True):
+        """The fixtures a shape overlaps (b2TestOverlap) at pose i = (x, y, angle): (offsets, items) as query_aabbs.
+        shapes: one Shape (every pose) or a list of them (shape_index picks one per pose; by default the i-th)."""
+        p = self._poses(poses)
+        table, ns, idx = self._shape_table(shapes, len(p), shape_index)
+        q = np.zeros(len(p), SHAPE_QUERY_DTYPE)
+        q["shape"] = idx
+        q["x"], q["y"], q["angle"] = p[:, 0], p[:, 1], p[:, 2]
+        return self._query(self.L.b2hip_query_shapes, q, len(q), mask, sensors, lead=(ns, C.cast(table, C.c_void_p)))
+
+    def shape_cast_closest(self, shapes, poses, translations, shape_index=None, mask=0xFFFF, sensors=True):
+        """The first fixture a shape meets moving from pose i by translation i (b2ShapeCast): a RAY_HIT_DTYPE array whose
+        fraction is the cast's lambda; fixture = -1 where it meets nothing (fixtures it overlaps at the pose included)."""
+        p = self._poses(poses)
+        t = self._pairs(translations, "translations")
+        if len(t) != len(p):
+            raise ValueError("shape_cast_closest: %d poses, %d translations" % (len(p), len(t)))
+        table, ns, idx = self._shape_table(shapes, len(p), shape_index)
+        c = np.zeros(len(p), SHAPE_CAST_DTYPE)
+        c["shape"] = idx
+        c["x"], c["y"], c["angle"] = p[:, 0], p[:, 1], p[:, 2]
+        c["tx"], c["ty"] = t[:, 0], t[:, 1]
+        out = np.zeros(len(c), RAY_HIT_DTYPE)
+        f = QueryFilter(mask, int(bool(sensors)))
+        _check(self.L.b2hip_shape_cast_closest(self.p, ns, C.cast(table, C.c_void_p), len(c), c.ctypes.data_as(C.c_void_p),
+                                               C.byref(f), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def solver_timing(self):

@@ -777,6 +777,50 @@ int b2hip_query_points(b2hip_world* w, int n, const float* points2n, const b2hip
                        b2hip_query_item* items);
 int b2hip_ray_cast_closest(b2hip_world* w, int n, const float* rays4n, const b2hip_query_filter* f, b2hip_ray_hit* out);
 
+/* ---- Batched shape queries on the device (same file, same kernels) --------------------------------------------------------
+ * The overlap and the closest linear cast of a convex shape, for many poses in one blocking call, on the same terms as the
+ * block above: the world of b2hip_get_fat_aabbs / b2hip_get_body_states at the call, pending edits uploaded first, the
+ * filter and the ids as above, refused inside an open step (B2HIP_ERR_INVALID) and on a sharded world
+ * (B2HIP_ERR_UNSUPPORTED), the same bytes run after run, a queried world stepping bit for bit like one that is not.
+ *
+ * shapes: n_shapes b2hip_shape records as b2hip_create_fixture takes them - a circle, an edge, a polygon (1 to 8 vertices)
+ *   or one child of a chain (type B2HIP_SHAPE_CHAIN, verts[0..3] the link's two vertices). A query names its shape by index,
+ *   so one probe shape serves any number of poses. A pose (x, y, angle) becomes a transform on the host (sinf / cosf, as
+ *   b2Rot::Set). A shape b2hip_create_fixture refuses, a polygon of no vertex, an index outside [0, n_shapes), n or
+ *   n_shapes outside [0, 2^24], a NULL input or output: B2HIP_ERR_INVALID before any device work.
+ * b2hip_query_shapes: every live proxy that passes the filter, whose fat AABB overlaps the query shape's AABB at the pose
+ *   (b2Shape::ComputeAABB; touching included), and whose shape overlaps the query shape there: b2TestOverlap(query shape,
+ *   0, fixture shape, child, pose, body transform), GJK distance with the radii below 10 FLT_EPSILON. Once each, in
+ *   ascending fixture id; offsets / cap / the returned total exactly as b2hip_query_aabbs. A NaN in a pose reports nothing.
+ * b2hip_shape_cast_closest: the query shape moves from its pose by (tx, ty). Candidates are the live proxies that pass the
+ *   filter and whose fat AABB overlaps the sweep box (the union of the shape's AABB at the pose and at the pose moved by
+ *   the translation); a candidate is hit when b2ShapeCast returns true with proxyA = the fixture's child at its body's
+ *   transform, proxyB = the query shape at the pose, translationB = (tx, ty) (the operand order of the Testbed's
+ *   ShapeCast test). out[i] is the hit of the smallest (lambda, fixture id): fraction = lambda, point and normal from
+ *   b2ShapeCast. A miss, a NaN or a non-finite translation gives fixture = body = -1, fraction = 1.
+ *   Start in overlap: a fixture whose core the shape's core already overlaps at its pose is NOT a hit (b2ShapeCast returns
+ *   false for it), and one whose skin alone it overlaps is hit at lambda 0 (b2ShapeCast's answer as well): ask
+ *   b2hip_query_shapes for what the shape overlaps at the start pose.
+ * Cost: each query or cast is one wave over the broad-phase grid. A query box or sweep box whose window has more than 4096
+ *   grid cells is walked in cell-long pieces of the translation (casts) or tests every proxy of the world (overlaps, and
+ *   casts longer than 4096 cells); so does a coordinate beyond 1e8 in magnitude. An overlap query with more than 4096 items
+ *   is put in order by two extra launches, as in b2hip_query_aabbs. Every candidate costs a GJK distance or shape cast. */
+typedef struct b2hip_shape_query
+{
+	int32_t shape;
+	float x, y, angle;
+} b2hip_shape_query; /* 16 bytes */
+typedef struct b2hip_shape_cast
+{
+	int32_t shape;
+	float x, y, angle, tx, ty;
+	int32_t pad[2];
+} b2hip_shape_cast; /* 32 bytes */
+int b2hip_query_shapes(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, int n, const b2hip_shape_query* queries,
+                       const b2hip_query_filter* f, int cap, int32_t* offsets, b2hip_query_item* items);
+int b2hip_shape_cast_closest(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, int n, const b2hip_shape_cast* casts,
+                             const b2hip_query_filter* f, b2hip_ray_hit* out);
+
 #ifdef __cplusplus
 }
 #endif
