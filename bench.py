@@ -8,7 +8,13 @@ revolving container that hangs on a motorised revolute joint (Testbed/Tests/Tumb
 measured in its SETTLED state: the boxes start on a grid that fills the container, have come down after ~400 steps and slosh
 until ~700 (the step time follows the contact count: SETTLE below), so the
 scene is stepped for SETTLE[...] untimed steps as part of building the workload whatever --warmup says (that transient is
-reported separately), then --warmup untimed steps, then exactly --steps timed steps. The other configurations are
+reported separately), then --warmup untimed steps, then exactly --steps timed steps.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does that and nothing else: it builds and settles the workload, warms up,
+times the N steps, writes --dump-outputs and prints the line (seconds beside the steps themselves). Everything that takes runs
+of its own - the 300-step distribution, the lazy read-back, the small-island roofline sample, the other configurations, the
+CPU baselines - is measured behind `--full` (minutes), after the timed steps and the dump, so that both kinds of run time the
+same steps. With --full the other configurations are
 `extra_configs` of the same line (config 2 = Pyramid 141, config 4's per-GPU share = Pyramid 316, config 5 on ONE GPU = the
 1 M-body field with 10 000 bullets), each in its own settled window with its own solver roofline and CPU baseline.
 
@@ -19,13 +25,15 @@ inside b2hip_step; "weak" scaling, `value` = container-steps/s = world steps/s x
 the reference's defaults - continuous physics ON); sleeping and warm starting are ON everywhere, on the GPU path and on the
 CPU baselines alike.
 
-One JSON line is printed by rank 0. Beside the contract's keys:
+One JSON line is printed by rank 0; `full` says which kind of run it was. Beside the contract's keys:
   roofline      the large-island SOLVER FAMILY of the timed workload - every kernel between the island build and
                 SynchronizeFixtures that works on the large islands (k_large_integrate / init / velocity, k_large_rest,
                 k_sweep_end, k_large_position, store_impulses, finalize, sleep), aggregated: SURVEY 8d's algorithmic bytes
                 of one solve / the family's duration per step, measured live with one HIP event pair per step on the world's
-                stream; `launches_per_step` says how many dependent launches that is. `traffic` = HBM bytes per step of
+                stream (over the last 5 warm-up steps, at no cost of its own; with --warmup below 5 it needs steps of its own behind the
+                timed ones and is there with --full only); `launches_per_step` says how many dependent launches that is. `traffic` = HBM bytes per step of
                 the same kernels from the committed rocprofv3 --pmc passes (profiles/, never sampled in-process).
+With --full only (beside `roofline_small_islands`, `extra_configs` and `ms_per_step_lazy_readback`):
   cpu_baseline  the reference build (oracle/_ref, kind "reference", 8 threads = b2_maxThreads) on the host: the SAME scene
                 in the SAME window where the reference can afford to get there inside its time budget - for the Tumbler
                 steps 60..79, with the GPU's figure for that very window beside it - and it says which window it is.
@@ -349,11 +357,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="tumbler", choices=["tumbler", "pyramid141"], help="the timed workload: BASELINE config 3 (default) or config 2")
     ap.add_argument("--tumbler", type=int, default=316, help="boxes per side of the Tumbler's grid (316 -> 99 856 boxes, BASELINE configs[2])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-long-window", action="store_true", help="skip the 300-step per-step distribution behind the timed region")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the multi-island roofline sample (500 k bodies in 100 k piles)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configs (Pyramid 141, 1 M field, 50 k pyramid)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of each CPU baseline (the headline's: twice that)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and --dump-outputs), also measure everything that takes runs of its own: the 300-step distribution, "
+                         "the lazy read-back, the small-island roofline sample, the other BASELINE configs and the CPU baselines (minutes; off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline of the timed workload")
+    ap.add_argument("--no-long-window", action="store_true", help="with --full: skip the 300-step per-step distribution behind the timed region")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the multi-island roofline sample (500 k bodies in 100 k piles)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other BASELINE configs (Pyramid 141, 1 M field, 50 k pyramid)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: time budget of each CPU baseline (the headline's: twice that)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one handed its caller (body states, a seeded sample of the contacts) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
@@ -487,15 +498,15 @@ def main():
         elapsed = float(t.item())
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, w)  # (the state the last timed step left, before anything else steps the world)
-    if roof is None:
-        roof = solver_roofline_pass()
+    if roof is None and args.full:
+        roof = solver_roofline_pass()  # (--warmup below ROOF_STEPS: a pass of its own behind the timed steps, so --full only)
     ctr = b2hip.Counters()
     hipL.b2hip_get_counters(dev, C.byref(ctr))
     contacts = w.contact_count
 
     # ---- the per-step distribution over 300 steps behind the timed region, whatever --steps was (not part of `value`)
     long_window = None
-    if not args.no_long_window:
+    if args.full and not args.no_long_window:
         try:
             first = settle + args.warmup + args.steps + (ROOF_STEPS if args.warmup < ROOF_STEPS else 0)
             long_window = distribution(time_steps(lambda: step_world(1), 300))
@@ -505,7 +516,7 @@ def main():
     # the same window length once more with the read-back on demand (b2hip_set_lazy_readback): nobody looks at a body between
     # these steps, the states come home once at the end (inside the timed region)
     lazy = None
-    if world_size == 1:
+    if args.full and world_size == 1:
         try:
             hipL.b2hip_set_lazy_readback.argtypes = [C.c_void_p, C.c_int]
             if hipL.b2hip_set_lazy_readback(dev, 1) == 0:
@@ -523,7 +534,7 @@ def main():
 
     # ---- secondary roofline: the in-LDS small-island kernel on a multi-island world (not part of `value`) ----------
     secondary = None
-    if world_size == 1 and not args.no_secondary:
+    if args.full and world_size == 1 and not args.no_secondary:
         try:
             w2 = amd.world(bh.PILES, 100000, 5, seed=3, flags=ccd)
             dev2 = w2.device_world()
@@ -539,7 +550,7 @@ def main():
 
     # ---- the other BASELINE configs (not part of `value`): config 2, the 1-GPU form of config 5, config 4's share ----
     extras = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         extras = []
         jobs = []
         if world_size == 1:
@@ -600,7 +611,7 @@ def main():
     # settled window (the Tumbler: ~0.1-0.3 s per step, 400 steps), so it is timed in a window it can reach - steps 60..79 -
     # and the GPU is timed in that very window beside it.
     cb = None
-    if world_size == 1 and not args.no_cpu_baseline:
+    if args.full and world_size == 1 and not args.no_cpu_baseline:
         cpu_first = 60 if args.workload == "tumbler" else settle + args.warmup
         cb = cpu_baseline_window(scene, p0, p1, flags, 1, cpu_first, 20, 2.0 * args.cpu_seconds)
         if cb is not None and "error" not in cb:
@@ -622,6 +633,7 @@ def main():
             "n_gpus": world_size,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": 1000.0 * elapsed / args.steps,
             "ms_per_step_p50": float(np.percentile(per_step_ms, 50)),
             "ms_per_step_p99": float(np.percentile(per_step_ms, 99)),

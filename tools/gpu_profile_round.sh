@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_round
 rm -rf $OUT; mkdir -p $OUT
 if [ "$1" != "notests" ]; then timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tail -3 | tee $OUT/pytest_gpu.txt; fi
-timeout 1200 python3 bench.py --steps 200 --warmup 60 2>$OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 1200 python3 bench.py --full --steps 200 --warmup 60 2>$OUT/bench.err | tail -1 > $OUT/bench.json
 # kernel trace of the bench command in steady state (the 240 settle steps are part of workload construction)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-secondary --no-extras --no-exact-order > $OUT/stats.log 2>&1
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv

@@ -13,7 +13,7 @@ if [ "${2:-}" != "notests" ]; then
   grep -a "passed\|failed" $OUT/pytest_gpu.txt | tail -2
   timeout 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -1 $OUT/smoke.txt
 fi
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_tumbler316.json 2> $OUT/bench.err
+timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_tumbler316.json 2> $OUT/bench.err
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-extras --no-long-window > $OUT/stats.log 2>&1
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $OUT/bench_tumbler316_kernel_stats.csv
 python3 tools/trace_steady.py /tmp/prof_stats 20 > $OUT/tumbler316_settled_steady_state_per_step.txt
