@@ -1,5 +1,5 @@
 // b2d_kernels_query.h - batched world queries between steps (b2hip_query_aabbs / b2hip_query_points / b2hip_ray_cast_closest /
-// b2hip_query_shapes / b2hip_shape_cast_closest).
+// b2hip_query_shapes / b2hip_shape_cast_closest / b2hip_shape_distance_closest / b2hip_query_shapes_within).
 //
 // Everything is read from the world's device state: the fat AABBs, the proxies' filters and shapes, the bodies' transforms,
 // and the hashed grid of b2d_kernels_broadphase.h, rebuilt from every proxy's box just before (gridRebuildNow). One WAVE per
@@ -10,7 +10,7 @@
 //
 // Determinism: the grid's order inside a bucket depends on arrival, so nothing here depends on it. Box, point and shape
 // queries sort each query's items by fixture id (k_query_sort, k_query_compact_big); rays and shape casts keep the smallest
-// (fraction bits, fixture) key, a total order.
+// (fraction bits, fixture) key, a total order; the closest distance keeps the smallest (distance bits, fixture) key.
 #ifndef B2D_KERNELS_QUERY_H
 #define B2D_KERNELS_QUERY_H
 
@@ -123,6 +123,7 @@ __device__ __forceinline__ void queryVisitAll(const DW& W, int lane, F& visit)
 
 // The record of one shape query or shape cast (b2hip_query_shapes / b2hip_shape_cast_closest): the pose as a transform the
 // host built (sinf / cosf there, as b2Rot::Set), the index of the query shape in the call's table, the cast's translation.
+// A distance query (b2hip_shape_distance_closest / b2hip_query_shapes_within) carries its max_distance in tx.
 struct QueryPose
 {
 	float x, y, c, s;
@@ -133,6 +134,7 @@ struct QueryPose
 #define QUERY_BOX 0
 #define QUERY_POINT 1
 #define QUERY_SHAPE 2
+#define QUERY_RANGE 3
 
 __device__ __forceinline__ Xf queryPoseXf(const QueryPose& qp)
 {
@@ -143,12 +145,50 @@ __device__ __forceinline__ Xf queryPoseXf(const QueryPose& qp)
 	return xf;
 }
 
+// a distance record is answered: a finite pose and a finite max_distance (QueryPose::tx) >= 0
+__device__ __forceinline__ bool queryRangeValid(const QueryPose& qp)
+{
+	return isfinite(qp.x) && isfinite(qp.y) && isfinite(qp.c) && isfinite(qp.s) && isfinite(qp.tx) && qp.tx >= 0.0f;
+}
+
+// b2Distance between the query shape at its pose (proxy A) and proxy q's shape at its body's transform (proxy B), with the
+// radii and from a zeroed cache: the value of the distance queries
+__device__ __forceinline__ GjkOutput queryDistance(const DW& W, int q, const GjkProxy& pQ, Xf xfQ)
+{
+	GjkCache cache;
+	cache.count = 0;
+	cache.metric = 0.0f;
+	for (int k = 0; k < 3; ++k) cache.indexA[k] = cache.indexB[k] = 0;
+	GjkOutput dist;
+	b2dDistance(dist, cache, pQ, xfQ, b2dProxy(W.shapes + W.p_shape[q]), loadXf(W.b_xf, W.p_body[q]), true);
+	return dist;
+}
+
+__device__ __forceinline__ b2hip_distance_hit queryDistanceRecord(const DW& W, int q, const GjkProxy& pQ, Xf xfQ)
+{
+	const GjkOutput dist = queryDistance(W, q, pQ, xfQ);
+	b2hip_distance_hit o;
+	o.fixture = q;
+	o.body = W.p_body[q];
+	o.point_ax = dist.pointA.x;
+	o.point_ay = dist.pointA.y;
+	o.point_bx = dist.pointB.x;
+	o.point_by = dist.pointB.y;
+	o.distance = dist.distance;
+	o.iterations = dist.iterations;
+	return o;
+}
+
 // Box, point and shape queries. pass 0: counts[i] = items of query i; pass 1: query i's items (fixture ids, unsorted) at
 // items[offsets[i] ...]. QUERY_POINT: boxes[i] = (x, y, x, y) and the shape must contain the point (b2dShapeTestPoint).
 // QUERY_SHAPE: the box is the query shape's AABB at its pose (b2Shape::ComputeAABB), computed by every lane from the
 // table, and a candidate must overlap the shape (b2TestOverlap: GJK distance with radii from a zeroed cache below
 // 10 epsilon; the query shape is proxy A, as in b2TestOverlap(query, 0, fixture, child, xfQ, xfBody)). Both proxies point
 // into global memory (W.shapes, the query table), so b2dSupport's run-time indexing stays out of scratch.
+// QUERY_RANGE (b2hip_query_shapes_within): the same box grown by the record's max_distance (QueryPose::tx) on every side, one
+// float operation per coordinate, and a candidate counts when that GJK distance is <= max_distance (queryDistance, the
+// value k_query_range_eval reports afterwards). A pose that is not finite, or a range that is NaN, negative or infinite:
+// nothing.
 template <int PASS, int KIND>
 __device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, const QueryPose* poses, const ShapeRec* qshapes, int n,
                                                uint32_t mask, int sensors, int* counts, const int* offsets, int* items)
@@ -161,15 +201,22 @@ __device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, const 
 		Xf xfQ;
 		GjkProxy pQ;
 		bool nan = false;
-		if (KIND == QUERY_SHAPE)
+		float range = 0.0f;
+		if (KIND == QUERY_SHAPE || KIND == QUERY_RANGE)
 		{
 			const QueryPose qp = poses[i];
 			nan = isnan(qp.x) || isnan(qp.y) || isnan(qp.c) || isnan(qp.s);
+			if (KIND == QUERY_RANGE)
+			{
+				range = qp.tx;
+				nan = !queryRangeValid(qp);
+			}
 			xfQ = queryPoseXf(qp);
 			const ShapeRec* rec = qshapes + qp.shape;
 			pQ = b2dProxy(rec);
 			const AABB qa = b2dShapeAABB(rec, xfQ);
 			b = make_float4(qa.lo.x, qa.lo.y, qa.hi.x, qa.hi.y);
+			if (KIND == QUERY_RANGE) b = make_float4(qa.lo.x - range, qa.lo.y - range, qa.hi.x + range, qa.hi.y + range);
 		}
 		else b = boxes[i];
 		if (nan || !(b.x <= b.z && b.y <= b.w)) // (lower > upper, or a NaN: nothing)
@@ -202,6 +249,7 @@ __device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, const 
 					b2dDistance(dist, cache, pQ, xfQ, b2dProxy(W.shapes + W.p_shape[q]), loadXf(W.b_xf, W.p_body[q]), true);
 					hit = dist.distance < 10.0f * B2D_EPSILON;
 				}
+				if (KIND == QUERY_RANGE && hit) hit = queryDistance(W, q, pQ, xfQ).distance <= range;
 			}
 			const unsigned long long m = __ballot(hit);
 			if (PASS == 1 && hit)
@@ -242,6 +290,16 @@ __global__ __launch_bounds__(256) void k_query_shapes_fill(DW W, const QueryPose
                                                            int sensors, const int* offsets, int* items)
 {
 	queryBoxesWave<1, QUERY_SHAPE>(W, nullptr, poses, qshapes, n, mask, sensors, nullptr, offsets, items);
+}
+__global__ __launch_bounds__(256) void k_query_ranges_count(DW W, const QueryPose* poses, const ShapeRec* qshapes, int n, uint32_t mask,
+                                                            int sensors, int* counts)
+{
+	queryBoxesWave<0, QUERY_RANGE>(W, nullptr, poses, qshapes, n, mask, sensors, counts, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void k_query_ranges_fill(DW W, const QueryPose* poses, const ShapeRec* qshapes, int n, uint32_t mask,
+                                                           int sensors, const int* offsets, int* items)
+{
+	queryBoxesWave<1, QUERY_RANGE>(W, nullptr, poses, qshapes, n, mask, sensors, nullptr, offsets, items);
 }
 
 // One workgroup per query: its items sorted ascending in LDS (bitonic network over the next power of two, padded with
@@ -539,6 +597,108 @@ __global__ __launch_bounds__(256) void k_query_shape_casts(DW W, const QueryPose
 				o.normal_y = r.normal.y;
 				o.fraction = r.lambda;
 			}
+			out[i] = o;
+		}
+	}
+}
+
+// The records of b2hip_query_shapes_within, after the sort (it moves bare fixture ids): one thread per item. Item k belongs
+// to the last query i with offsets[i] <= k (a search over offsets[0 .. n]; empty queries share an offset with the next one);
+// its distance is computed again, as the fill pass computed it, and written out whole.
+__global__ __launch_bounds__(256) void k_query_range_eval(DW W, const QueryPose* poses, const ShapeRec* qshapes, int n, const int* offsets,
+                                                          const int* items, int nItems, b2hip_distance_hit* out)
+{
+	for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < nItems; k += (int)(gridDim.x * blockDim.x))
+	{
+		int lo = 0, hi = n; // (offsets[lo] <= k < offsets[hi])
+		while (hi - lo > 1)
+		{
+			const int mid = (lo + hi) >> 1;
+			if (offsets[mid] <= k) lo = mid; else hi = mid;
+		}
+		const QueryPose qp = poses[lo];
+		out[k] = queryDistanceRecord(W, items[k], b2dProxy(qshapes + qp.shape), queryPoseXf(qp));
+	}
+}
+
+// Closest fixture within a range, one WAVE per query (b2hip_shape_distance_closest). The query box is the query shape's AABB
+// at the pose grown by max_distance; a candidate is a live proxy passing the filter whose fat AABB overlaps the WHOLE query
+// box, whichever cells it was found in, and whose distance (queryDistance) is <= max_distance; best = the smallest
+// (distance bits, fixture id) - distances are >= +0, so their bits order like the values. The walk does not pay for the
+// whole range when something is near: large proxies first, then the grid windows of the shape's box grown by r = one cell,
+// then 2, 4, ... cells, the last ring being the whole query box; it stops once the best distance is below r - margin. Why
+// that is sound: queryVisitGrid shows every grid-sized proxy whose fat box overlaps the ring's box, so one not yet seen has
+// a fat box clear of the shape's box by more than r on some axis. The shape's box holds the query shape with its skin and a
+// fat box the fixture's with its skin - except for a chain link, whose box leaves its b2_polygonRadius out - so the
+// unseen proxy is farther than r - 2 b2_polygonRadius: margin = those plus the rounding term the rays and casts use. A
+// proxy whose fat box overlaps the previous ring's box was evaluated there and is skipped (the minimum would not change).
+// A ring of more than QUERY_WINDOW_MAX cells, or a coordinate beyond QUERY_COORD_MAX, scans every proxy of the world.
+__global__ __launch_bounds__(256) void k_query_shape_distances(DW W, const QueryPose* poses, const ShapeRec* qshapes, int n, uint32_t mask,
+                                                               int sensors, b2hip_distance_hit* out)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const int nWaves = (int)((gridDim.x * blockDim.x) >> 6);
+	for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nWaves)
+	{
+		const QueryPose qp = poses[i];
+		const ShapeRec* rec = qshapes + qp.shape;
+		const GjkProxy pQ = b2dProxy(rec);
+		const Xf xfQ = queryPoseXf(qp);
+		const float range = qp.tx;
+		unsigned long long best = ~0ull;
+		if (queryRangeValid(qp))
+		{
+			const AABB box0 = b2dShapeAABB(rec, xfQ);
+			const float4 whole = make_float4(box0.lo.x - range, box0.lo.y - range, box0.hi.x + range, box0.hi.y + range);
+			const float mag = fmaxf(fmaxf(fabsf(whole.x), fabsf(whole.y)), fmaxf(fabsf(whole.z), fabsf(whole.w)));
+			const float margin = 1.0e-3f + 1.0e-5f * mag + 2.0f * B2D_POLYGON_RADIUS;
+			const float inf = __uint_as_float(0x7f800000u);
+			float4 done = make_float4(inf, inf, -inf, -inf); // the ring already evaluated (none yet: lower = +inf overlaps no box)
+			auto visit = [&](bool valid, int q, float4 fat)
+			{
+				bool cand = valid && !(fat.x > whole.z || fat.y > whole.w || whole.x > fat.z || whole.y > fat.w);
+				if (cand) cand = fat.x > done.z || fat.y > done.w || done.x > fat.z || done.y > fat.w;
+				if (cand) cand = queryFilterPasses(W, q, mask, sensors);
+				if (cand)
+				{
+					const float dist = queryDistance(W, q, pQ, xfQ).distance;
+					if (dist <= range)
+					{
+						const unsigned long long key = ((unsigned long long)__float_as_uint(dist) << 32) | (uint32_t)q;
+						best = key < best ? key : best;
+					}
+				}
+			};
+			queryVisitLarge(W, lane, visit);
+			bool all = !(mag <= QUERY_COORD_MAX);
+			if (!all)
+			{
+				for (float r = fmaxf(gridCell(W), B2D_LINEAR_SLOP);; r *= 2.0f) // (never 0: the rings must grow)
+				{
+					const bool last = !(r < range);
+					const float4 box = last ? whole : make_float4(box0.lo.x - r, box0.lo.y - r, box0.hi.x + r, box0.hi.y + r);
+					if (!queryVisitGrid(W, lane, box, visit))
+					{
+						all = true;
+						break;
+					}
+					best = waveMinU64(best);
+					if (last || (best != ~0ull && __uint_as_float((uint32_t)(best >> 32)) < r - margin)) break;
+					done = box;
+				}
+			}
+			if (all) queryVisitAll(W, lane, visit);
+			best = waveMinU64(best);
+		}
+		if (lane == 0)
+		{
+			b2hip_distance_hit o;
+			o.fixture = -1;
+			o.body = -1;
+			o.point_ax = o.point_ay = o.point_bx = o.point_by = 0.0f;
+			o.distance = __uint_as_float(0x7f800000u);
+			o.iterations = 0;
+			if (best != ~0ull) o = queryDistanceRecord(W, (int)(uint32_t)best, pQ, xfQ); // (the kept candidate again)
 			out[i] = o;
 		}
 	}

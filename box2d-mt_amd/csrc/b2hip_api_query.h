@@ -1,4 +1,4 @@
-// b2hip_api_query.h - batched AABB, point, shape-overlap, closest-ray and closest-shape-cast queries between steps
+// b2hip_api_query.h - batched AABB, point, shape-overlap, closest-ray, closest-shape-cast and distance queries between steps
 // (include/b2hip.h; kernels: b2d_kernels_query.h).
 //
 // What a query sees: the edits made since the last step are uploaded first (flushEdits - what the next step's first call
@@ -84,9 +84,10 @@ static int queryShapesCheck(const char* what, int nShapes, const b2hip_shape* sh
 	return 0;
 }
 
-// n QueryPose records (the pose's rotation by the host's sinf / cosf, as b2Rot::Set) and the shape table into the pinned buffer
+// n QueryPose records (the pose's rotation by the host's sinf / cosf, as b2Rot::Set) and the shape table into the pinned
+// buffer, from whichever of queries / casts / ranges is given (a range's max_distance travels in tx)
 static int queryShapesStage(b2hip_world* w, int n, const std::vector<ShapeRec>& recs, const b2hip_shape_query* queries,
-                            const b2hip_shape_cast* casts, size_t atLeast)
+                            const b2hip_shape_cast* casts, size_t atLeast, const b2hip_shape_range* ranges = nullptr)
 {
 	const size_t bytes = (size_t)n * sizeof(QueryPose) + recs.size() * sizeof(ShapeRec);
 	if (int rc = queryPinned(w, std::max(bytes, atLeast))) return rc;
@@ -94,6 +95,18 @@ static int queryShapesStage(b2hip_world* w, int n, const std::vector<ShapeRec>& 
 	for (int i = 0; i < n; ++i)
 	{
 		QueryPose& r = stage[i];
+		if (ranges)
+		{
+			r.x = ranges[i].x;
+			r.y = ranges[i].y;
+			r.s = sinf(ranges[i].angle);
+			r.c = cosf(ranges[i].angle);
+			r.tx = ranges[i].max_distance;
+			r.ty = 0.0f;
+			r.shape = ranges[i].shape;
+			r.pad = 0;
+			continue;
+		}
 		const float angle = queries ? queries[i].angle : casts[i].angle;
 		r.x = queries ? queries[i].x : casts[i].x;
 		r.y = queries ? queries[i].y : casts[i].y;
@@ -124,11 +137,14 @@ static int queryEnd(b2hip_world* w)
 	return 0;
 }
 
-// Box, point and shape queries: a count pass, a scan, a fill pass, the sort. `in` is 4n floats of boxes or 2n of points; a
-// shape query passes recs (the checked query shapes) and queries instead.
+// Box, point, shape and within-range queries: a count pass, a scan, a fill pass, the sort. `in` is 4n floats of boxes or 2n of
+// points; a shape query passes recs (the checked query shapes) and queries instead, a within-range query recs, ranges and
+// hits: its sorted ids become full records on the device (k_query_range_eval), the first min(total, cap) of them.
 static int queryBoxes(b2hip_world* w, const char* what, int n, const float* in, int kind, const std::vector<ShapeRec>* recs,
-                      const b2hip_shape_query* queries, const b2hip_query_filter* f, int cap, int32_t* offsets, b2hip_query_item* items)
+                      const b2hip_shape_query* queries, const b2hip_query_filter* f, int cap, int32_t* offsets, b2hip_query_item* items,
+                      const b2hip_shape_range* ranges = nullptr, b2hip_distance_hit* hits = nullptr)
 {
+	const bool shaped = kind == QUERY_SHAPE || kind == QUERY_RANGE;
 	if (int rc = queryUsable(w, what)) return rc;
 	DEVICE_GUARD(w);
 	const uint32_t mask = f ? (uint32_t)f->mask : 0xffffu;
@@ -137,9 +153,9 @@ static int queryBoxes(b2hip_world* w, const char* what, int n, const float* in, 
 	if (n == 0) return 0;
 	const size_t offsetBytes = ((size_t)n + 1) * sizeof(int);
 	int rc;
-	if (kind == QUERY_SHAPE)
+	if (shaped)
 	{
-		rc = queryShapesStage(w, n, *recs, queries, nullptr, offsetBytes);
+		rc = queryShapesStage(w, n, *recs, queries, nullptr, offsetBytes, ranges);
 		if (rc) return rc;
 	}
 	else
@@ -151,7 +167,7 @@ static int queryBoxes(b2hip_world* w, const char* what, int n, const float* in, 
 			stage[i] = kind == QUERY_POINT ? make_float4(in[2 * (size_t)i], in[2 * (size_t)i + 1], in[2 * (size_t)i], in[2 * (size_t)i + 1])
 			                               : make_float4(in[4 * (size_t)i], in[4 * (size_t)i + 1], in[4 * (size_t)i + 2], in[4 * (size_t)i + 3]);
 	}
-	rc = queryBegin(w, n, true, kind == QUERY_SHAPE ? (int)recs->size() : -1);
+	rc = queryBegin(w, n, true, shaped ? (int)recs->size() : -1);
 	if (rc) return rc;
 	hipStream_t s = w->stream;
 	DW& d = w->dw;
@@ -165,7 +181,8 @@ static int queryBoxes(b2hip_world* w, const char* what, int n, const float* in, 
 	}
 	else
 	{
-		if (kind == QUERY_SHAPE) LAUNCH(w, k_query_shapes_count, waveBlocks, 256, d, poses, qshapes, n, mask, sensors, w->qCounts.p);
+		if (kind == QUERY_RANGE) LAUNCH(w, k_query_ranges_count, waveBlocks, 256, d, poses, qshapes, n, mask, sensors, w->qCounts.p);
+		else if (kind == QUERY_SHAPE) LAUNCH(w, k_query_shapes_count, waveBlocks, 256, d, poses, qshapes, n, mask, sensors, w->qCounts.p);
 		else if (kind == QUERY_POINT) LAUNCH(w, k_query_points_count, waveBlocks, 256, d, boxes, n, mask, sensors, w->qCounts.p);
 		else LAUNCH(w, k_query_aabbs_count, waveBlocks, 256, d, boxes, n, mask, sensors, w->qCounts.p);
 		deviceExclusiveScan<int>(s, w->qCounts.p, w->qOffsets.p, w->qScanWork.p, w->qScan, w->qWords.p, n);
@@ -182,7 +199,8 @@ static int queryBoxes(b2hip_world* w, const char* what, int n, const float* in, 
 		rc = w->qItems.ensure((size_t)total, s, false, false);
 		if (rc) return rc;
 		const int* offs = (const int*)w->qOffsets.p;
-		if (kind == QUERY_SHAPE) LAUNCH(w, k_query_shapes_fill, waveBlocks, 256, d, poses, qshapes, n, mask, sensors, offs, w->qItems.p);
+		if (kind == QUERY_RANGE) LAUNCH(w, k_query_ranges_fill, waveBlocks, 256, d, poses, qshapes, n, mask, sensors, offs, w->qItems.p);
+		else if (kind == QUERY_SHAPE) LAUNCH(w, k_query_shapes_fill, waveBlocks, 256, d, poses, qshapes, n, mask, sensors, offs, w->qItems.p);
 		else if (kind == QUERY_POINT) LAUNCH(w, k_query_points_fill, waveBlocks, 256, d, boxes, n, mask, sensors, offs, w->qItems.p);
 		else LAUNCH(w, k_query_aabbs_fill, waveBlocks, 256, d, boxes, n, mask, sensors, offs, w->qItems.p);
 		LAUNCH(w, k_query_sort, gridFor((size_t)n, 1, 16384), QUERY_SORT_THREADS, offs, n, w->qItems.p);
@@ -196,9 +214,26 @@ static int queryBoxes(b2hip_world* w, const char* what, int n, const float* in, 
 			LAUNCH(w, k_query_compact_big, 1, 1024, w->qFlags.p, d.nProxies, w->qItems.p + offsets[i]);
 		}
 	}
+	const int copy = std::min(total, cap);
+	if (kind == QUERY_RANGE)
+	{
+		if (copy > 0)
+		{
+			rc = w->qDistances.ensure((size_t)copy, s, false, false);
+			if (rc) return rc;
+			LAUNCH(w, k_query_range_eval, gridFor((size_t)copy), 256, d, poses, qshapes, n, (const int*)w->qOffsets.p, (const int*)w->qItems.p, copy,
+			       w->qDistances.p);
+		}
+		rc = queryEnd(w);
+		if (rc) return rc;
+		if ((rc = queryPinned(w, (size_t)copy * sizeof(b2hip_distance_hit)))) return rc; // (the offsets have left it)
+		if (copy > 0) HIP_TRY(hipMemcpyAsync(w->qPinned, w->qDistances.p, (size_t)copy * sizeof(b2hip_distance_hit), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (copy > 0) memcpy(hits, w->qPinned, (size_t)copy * sizeof(b2hip_distance_hit));
+		return total;
+	}
 	rc = queryEnd(w);
 	if (rc) return rc;
-	const int copy = std::min(total, cap);
 	if ((rc = queryPinned(w, (size_t)copy * sizeof(int)))) return rc; // (the offsets have left it)
 	int* hItems = (int*)w->qPinned;
 	if (copy > 0) HIP_TRY(hipMemcpyAsync(hItems, w->qItems.p, (size_t)copy * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -211,7 +246,7 @@ static int queryBoxes(b2hip_world* w, const char* what, int n, const float* in, 
 	return total;
 }
 
-static int queryListArgs(const char* what, int n, const void* in, int cap, int32_t* offsets, b2hip_query_item* items)
+static int queryListArgs(const char* what, int n, const void* in, int cap, int32_t* offsets, const void* items)
 {
 	if (n < 0 || n > B2HIP_QUERY_MAX) return setError(B2HIP_ERR_INVALID, std::string(what) + ": n must lie in [0, 2^24]");
 	if (cap < 0) return setError(B2HIP_ERR_INVALID, std::string(what) + ": negative cap");
@@ -327,4 +362,65 @@ int b2hip_shape_cast_closest(b2hip_world* w, int n_shapes, const b2hip_shape* sh
 	if ((rc = queryScanAborted(w, what))) return rc;
 	memcpy(out, w->qPinned, (size_t)n * sizeof(b2hip_ray_hit));
 	return B2HIP_OK;
+}
+
+// the misses of a closest-distance batch (an empty world answers every record with one)
+static void queryDistanceMisses(int n, b2hip_distance_hit* out)
+{
+	for (int i = 0; i < n; ++i)
+	{
+		memset(&out[i], 0, sizeof(b2hip_distance_hit));
+		out[i].fixture = out[i].body = -1;
+		out[i].distance = INFINITY;
+	}
+}
+
+int b2hip_shape_distance_closest(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, int n, const b2hip_shape_range* ranges,
+                                 const b2hip_query_filter* f, b2hip_distance_hit* out)
+{
+	const char* what = "b2hip_shape_distance_closest";
+	if (n < 0 || n > B2HIP_QUERY_MAX) return setError(B2HIP_ERR_INVALID, std::string(what) + ": n must lie in [0, 2^24]");
+	if (n_shapes < 0 || n_shapes > B2HIP_QUERY_MAX) return setError(B2HIP_ERR_INVALID, std::string(what) + ": n_shapes must lie in [0, 2^24]");
+	if (!out || (n > 0 && !ranges) || (n_shapes > 0 && !shapes)) return setError(B2HIP_ERR_INVALID, std::string(what) + ": null input or output");
+	std::vector<ShapeRec> recs;
+	if (int rc = queryShapesCheck(what, n_shapes, shapes, n, n > 0 ? &ranges[0].shape : nullptr, sizeof(b2hip_shape_range), recs)) return rc;
+	if (int rc = queryUsable(w, what)) return rc;
+	DEVICE_GUARD(w);
+	if (n == 0) return B2HIP_OK;
+	const uint32_t mask = f ? (uint32_t)f->mask : 0xffffu;
+	const int sensors = f ? (f->include_sensors != 0) : 1;
+	int rc = queryShapesStage(w, n, recs, nullptr, nullptr, (size_t)n * sizeof(b2hip_distance_hit), ranges);
+	if (rc) return rc;
+	rc = queryBegin(w, n, false, n_shapes);
+	if (rc) return rc;
+	hipStream_t s = w->stream;
+	DW& d = w->dw;
+	if (d.nProxies == 0)
+	{
+		queryDistanceMisses(n, out);
+		return B2HIP_OK;
+	}
+	rc = w->qDistances.ensure((size_t)n, s, false, false);
+	if (rc) return rc;
+	LAUNCH(w, k_query_shape_distances, gridFor((size_t)n * 64, 256, 8192), 256, d, (const QueryPose*)w->qPoses.p, (const ShapeRec*)w->qShapes.p,
+	       n, mask, sensors, w->qDistances.p);
+	rc = queryEnd(w);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(w->qPinned, w->qDistances.p, (size_t)n * sizeof(b2hip_distance_hit), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if ((rc = queryScanAborted(w, what))) return rc;
+	memcpy(out, w->qPinned, (size_t)n * sizeof(b2hip_distance_hit));
+	return B2HIP_OK;
+}
+
+int b2hip_query_shapes_within(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, int n, const b2hip_shape_range* ranges,
+                              const b2hip_query_filter* f, int cap, int32_t* offsets, b2hip_distance_hit* hits)
+{
+	const char* what = "b2hip_query_shapes_within";
+	if (int rc = queryListArgs(what, n, ranges, cap, offsets, hits)) return rc;
+	if (n_shapes < 0 || n_shapes > B2HIP_QUERY_MAX) return setError(B2HIP_ERR_INVALID, std::string(what) + ": n_shapes must lie in [0, 2^24]");
+	if (n_shapes > 0 && !shapes) return setError(B2HIP_ERR_INVALID, std::string(what) + ": null input or output");
+	std::vector<ShapeRec> recs;
+	if (int rc = queryShapesCheck(what, n_shapes, shapes, n, n > 0 ? &ranges[0].shape : nullptr, sizeof(b2hip_shape_range), recs)) return rc;
+	return queryBoxes(w, what, n, nullptr, QUERY_RANGE, &recs, nullptr, f, cap, offsets, nullptr, ranges, hits);
 }

@@ -197,6 +197,7 @@ struct b2hip_world
 	DevArray<float4> qIn;
 	DevArray<int> qCounts, qOffsets, qItems, qFlags, qScanWork, qScanWords, qWords;
 	DevArray<b2hip_ray_hit> qHits;
+	DevArray<b2hip_distance_hit> qDistances; // the records of the distance queries
 	DevArray<QueryPose> qPoses; // shape queries and casts: pose, shape index, translation per query
 	DevArray<ShapeRec> qShapes; // ... and the call's query shapes (the GJK proxies point into this table)
 	ScanFlags qScan;

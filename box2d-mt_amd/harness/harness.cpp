@@ -773,6 +773,57 @@ int b2h_shape_cast_all(b2h_world* h, const b2hip_shape* s, float x, float y, flo
 	}
 	return n;
 }
+
+// b2hip_shape_distance_closest / b2hip_query_shapes_within composed from the drop-in: b2World::QueryAABB over the query
+// shape's box at the pose with max_distance subtracted from both lower coordinates and added to both upper ones, then
+// b2Distance for each reported proxy with proxyA = the query shape at the pose, proxyB = the fixture's child at its body's
+// transform, the radii and a zeroed cache. EVERY proxy with distance <= max_distance, in ascending fixture id: ids3[3 k] its
+// device fixture id, body id and b2DistanceOutput::iterations, out5[5 k] (distance, pointA.x, pointA.y, pointB.x, pointB.y);
+// returns their number (up to cap written). Nothing for a pose that is not finite or a range that is NaN, negative or
+// infinite.
+int b2h_shape_distance_all(b2h_world* h, const b2hip_shape* s, float x, float y, float angle, float max_distance, int cap, int* ids3,
+                           float* out5)
+{
+	if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(angle) || !std::isfinite(max_distance) || !(max_distance >= 0.0f)) return 0;
+	QueryShape q(*s);
+	b2Transform xf;
+	xf.Set(b2Vec2(x, y), angle);
+	b2AABB box;
+	q.shape->ComputeAABB(&box, xf, 0);
+	box.lowerBound.x = box.lowerBound.x - max_distance;
+	box.lowerBound.y = box.lowerBound.y - max_distance;
+	box.upperBound.x = box.upperBound.x + max_distance;
+	box.upperBound.y = box.upperBound.y + max_distance;
+	std::vector<std::pair<const b2Fixture*, int> > proxies;
+	proxiesOver(h, box, proxies);
+	int n = 0;
+	for (const auto& pc : proxies)
+	{
+		b2DistanceInput in;
+		in.proxyA = q.proxy;
+		in.proxyB.Set(pc.first->GetShape(), pc.second);
+		in.transformA = xf;
+		in.transformB = pc.first->GetBody()->GetTransform();
+		in.useRadii = true;
+		b2SimplexCache cache;
+		memset(&cache, 0, sizeof(cache));
+		b2DistanceOutput o;
+		b2Distance(&o, &cache, &in);
+		if (!(o.distance <= max_distance)) continue;
+		if (n < cap)
+		{
+			ids3[3 * n] = pc.first->GetDeviceId() + pc.second;
+			ids3[3 * n + 1] = pc.first->GetBody()->GetDeviceId();
+			ids3[3 * n + 2] = o.iterations;
+			float* r = out5 + 5 * n;
+			r[0] = o.distance;
+			r[1] = o.pointA.x; r[2] = o.pointA.y;
+			r[3] = o.pointB.x; r[4] = o.pointB.y;
+		}
+		++n;
+	}
+	return n;
+}
 #endif
 
 // Dumps every contact of the world's contact list.

@@ -136,6 +136,9 @@ RAY_HIT_DTYPE = np.dtype([("fixture", "i4"), ("body", "i4"), ("point", "f4", 2),
 SHAPE_QUERY_DTYPE = np.dtype([("shape", "i4"), ("x", "f4"), ("y", "f4"), ("angle", "f4")])
 SHAPE_CAST_DTYPE = np.dtype([("shape", "i4"), ("x", "f4"), ("y", "f4"), ("angle", "f4"), ("tx", "f4"), ("ty", "f4"),
                              ("pad", "i4", 2)])
+SHAPE_RANGE_DTYPE = np.dtype([("shape", "i4"), ("x", "f4"), ("y", "f4"), ("angle", "f4"), ("max_distance", "f4"), ("pad", "i4")])
+DISTANCE_HIT_DTYPE = np.dtype([("fixture", "i4"), ("body", "i4"), ("point_a", "f4", 2), ("point_b", "f4", 2), ("distance", "f4"),
+                               ("iterations", "i4")])
 
 _lib = None
 
@@ -206,6 +209,10 @@ def _configure(L, optional_ok=False):
                                C.c_void_p, C.c_void_p],
         "b2hip_shape_cast_closest": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter),
                                      C.c_void_p],
+        "b2hip_shape_distance_closest": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter),
+                                         C.c_void_p],
+        "b2hip_query_shapes_within": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int,
+                                      C.c_void_p, C.c_void_p],
     }
     for name, argtypes in sigs.items():
         try:
@@ -560,16 +567,16 @@ class World:
             raise ValueError("%s: an (n, 2) array is expected, got shape %s" % (name, a.shape))
         return a
 
-    def _query(self, fn, data, n, mask, sensors, lead=()):
+    def _query(self, fn, data, n, mask, sensors, lead=(), dtype=QUERY_ITEM_DTYPE):
         f = QueryFilter(mask, int(bool(sensors)))
         offsets = np.zeros(n + 1, np.int32)
-        items = np.zeros(max(n, 1) * 8, QUERY_ITEM_DTYPE)
+        items = np.zeros(max(n, 1) * 8, dtype)
         for _ in range(2):  # (once more with the exact capacity when the first guess was short)
             total = _check(fn(self.p, *lead, n, data.ctypes.data_as(C.c_void_p), C.byref(f), items.size,
                               offsets.ctypes.data_as(C.c_void_p), items.ctypes.data_as(C.c_void_p)))
             if total <= items.size:
                 return offsets, items[:total]
-            items = np.zeros(total, QUERY_ITEM_DTYPE)
+            items = np.zeros(total, dtype)
         raise B2HipError("query: the result grew between two identical calls")
 
     def query_aabbs(self, lower, upper, mask=0xFFFF, sensors=True):
@@ -648,6 +655,38 @@ class World:
         _check(self.L.b2hip_shape_cast_closest(self.p, ns, C.cast(table, C.c_void_p), len(c), c.ctypes.data_as(C.c_void_p),
                                                C.byref(f), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    @staticmethod
+    def _ranges(shapes, poses, max_distance, shape_index):
+        """(SHAPE_RANGE_DTYPE records, shape count, Shape array) of a distance batch"""
+        p = World._poses(poses)
+        table, ns, idx = World._shape_table(shapes, len(p), shape_index)
+        r = np.zeros(len(p), SHAPE_RANGE_DTYPE)
+        r["shape"] = idx
+        r["x"], r["y"], r["angle"] = p[:, 0], p[:, 1], p[:, 2]
+        d = np.asarray(max_distance, np.float32)
+        if d.ndim > 1 or (d.ndim == 1 and len(d) != len(p)):
+            raise ValueError("max_distance: a scalar or an (n,) array is expected, got shape %s for %d poses" % (d.shape, len(p)))
+        r["max_distance"] = d
+        return r, ns, table
+
+    def shape_distance_closest(self, shapes, poses, max_distance, shape_index=None, mask=0xFFFF, sensors=True):
+        """The nearest fixture within max_distance (a scalar or one per pose) of a shape at pose i = (x, y, angle), by
+        b2Distance with the radii: a DISTANCE_HIT_DTYPE array with the distance and the closest points on the shape (point_a)
+        and on the fixture (point_b); fixture = -1 and distance = inf where nothing is within range. 0 where they overlap."""
+        r, ns, table = self._ranges(shapes, poses, max_distance, shape_index)
+        out = np.zeros(len(r), DISTANCE_HIT_DTYPE)
+        f = QueryFilter(mask, int(bool(sensors)))
+        _check(self.L.b2hip_shape_distance_closest(self.p, ns, C.cast(table, C.c_void_p), len(r), r.ctypes.data_as(C.c_void_p),
+                                                   C.byref(f), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def query_shapes_within(self, shapes, poses, max_distance, shape_index=None, mask=0xFFFF, sensors=True):
+        """Every fixture within max_distance of a shape at pose i: (offsets[n + 1], hits) with hits[offsets[i]:offsets[i + 1]]
+        the DISTANCE_HIT_DTYPE records of pose i in ascending fixture id."""
+        r, ns, table = self._ranges(shapes, poses, max_distance, shape_index)
+        return self._query(self.L.b2hip_query_shapes_within, r, len(r), mask, sensors, lead=(ns, C.cast(table, C.c_void_p)),
+                           dtype=DISTANCE_HIT_DTYPE)
 
     def solver_timing(self):
         ms, by, ct, b = C.c_float(), C.c_double(), C.c_int(), C.c_int()

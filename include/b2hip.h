@@ -821,6 +821,65 @@ int b2hip_query_shapes(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, 
 int b2hip_shape_cast_closest(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, int n, const b2hip_shape_cast* casts,
                              const b2hip_query_filter* f, b2hip_ray_hit* out);
 
+/* ---- Batched distance queries on the device (same file, same kernels) -----------------------------------------------------
+ * How far the nearest fixture is and where (b2hip_shape_distance_closest), or every fixture within a range with its
+ * distance and closest points (b2hip_query_shapes_within), for many poses of a convex shape in one blocking call; on the
+ * same terms as the two blocks above: the world of b2hip_get_fat_aabbs / b2hip_get_body_states at the call, pending edits
+ * uploaded first, the filter, the ids and the shape table as above, refused inside an open step (B2HIP_ERR_INVALID) and on
+ * a sharded world (B2HIP_ERR_UNSUPPORTED), the same bytes run after run, a queried world stepping bit for bit like one
+ * that is not. Each call runs on the world's stream and returns when the results are on the host.
+ *
+ * Candidates: the query box is the query shape's AABB at the pose (b2Shape::ComputeAABB) with max_distance subtracted from
+ *   both lower coordinates and added to both upper ones (one float operation each). The candidates are exactly the live
+ *   proxies that pass the filter and whose fat AABB overlaps that box, touching included: the set b2World::QueryAABB
+ *   reports over it. So the answer does not depend on how the grid is walked. (A fat AABB holds its fixture's shape, so a
+ *   fixture within max_distance is a candidate; only a chain link's box leaves its b2_polygonRadius skin out.)
+ * Value: b2Distance with proxyA = the query shape (child 0) at the pose, proxyB = the fixture's child at its body's
+ *   transform, useRadii = true and a zeroed cache - the orientation of b2TestOverlap and b2hip_query_shapes. point_a lies
+ *   on the query shape, point_b on the fixture, both on the skins (the radii are applied); iterations is
+ *   b2DistanceOutput::iterations. A candidate counts when distance <= max_distance. Shapes that overlap give distance 0
+ *   and both points at the midpoint of the cores' closest points, as b2Distance does. max_distance = 0 therefore reports
+ *   the fixtures at distance == 0 only: NOT the `< 10 FLT_EPSILON` rule of b2hip_query_shapes, which also passes a
+ *   positive distance below that bound.
+ * b2hip_shape_distance_closest: out[i] is the candidate with the smallest (distance, fixture id): distances are >= +0, so
+ *   their bits order like their values, and ties go to the LOWER fixture id. Nothing within range: fixture = body = -1,
+ *   the four point coordinates 0, iterations = 0, distance = +infinity. Returns B2HIP_OK or a b2hip_status.
+ * b2hip_query_shapes_within: every counting candidate once, in ascending fixture id, each with its full record. offsets
+ *   (n + 1) are always complete, hits receives the first min(total, cap) records, the total is returned (or a
+ *   b2hip_status): when it exceeds cap, call again with cap = the total - exactly as b2hip_query_aabbs.
+ * Invalid records: a pose with a NaN or non-finite component, a max_distance that is NaN, negative or infinite. The closest
+ *   call answers one with the miss above, the within call with an empty list.
+ * Argument errors, refused with B2HIP_ERR_INVALID before any device work: n or n_shapes outside [0, 2^24], a NULL input or
+ *   output, a negative cap, a shape b2hip_create_fixture refuses, a polygon of no vertex, a shape index outside
+ *   [0, n_shapes).
+ * Cost: one wave per query. The closest call visits the large proxies, then the grid cells around the shape's box in
+ *   rings of 1, 2, 4, ... cells and stops once the best distance found is below the ring's reach: something near costs a
+ *   few cells whatever max_distance is. With nothing near it walks out to the whole query box, and a ring of more than
+ *   4096 grid cells - or a coordinate beyond 1e8 in magnitude - tests every proxy of the world from that one wave (10^6
+ *   candidates on a 10^6-body world): the slow case, so keep max_distance near what the caller needs. The within call
+ *   walks the whole query box in a count and a fill pass (more than 4096 cells: every proxy, twice), sorts, and evaluates
+ *   each reported record once more; a list of more than 4096 records is put in order by two extra launches, as in
+ *   b2hip_query_aabbs. Every candidate costs a GJK distance. */
+typedef struct b2hip_shape_range
+{
+	int32_t shape;       /* index into `shapes` */
+	float x, y, angle;   /* pose of the query shape */
+	float max_distance;  /* finite, >= 0 */
+	int32_t pad;
+} b2hip_shape_range; /* 24 bytes */
+typedef struct b2hip_distance_hit
+{
+	int32_t fixture, body;   /* -1, -1: nothing within range */
+	float point_ax, point_ay; /* closest point on the query shape */
+	float point_bx, point_by; /* closest point on the fixture */
+	float distance;
+	int32_t iterations;      /* b2DistanceOutput::iterations */
+} b2hip_distance_hit; /* 32 bytes */
+int b2hip_shape_distance_closest(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, int n, const b2hip_shape_range* ranges,
+                                 const b2hip_query_filter* f, b2hip_distance_hit* out);
+int b2hip_query_shapes_within(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, int n, const b2hip_shape_range* ranges,
+                              const b2hip_query_filter* f, int cap, int32_t* offsets, b2hip_distance_hit* hits);
+
 #ifdef __cplusplus
 }
 #endif
