@@ -1,5 +1,6 @@
 // b2d_kernels_query.h - batched world queries between steps (b2hip_query_aabbs / b2hip_query_points / b2hip_ray_cast_closest /
-// b2hip_query_shapes / b2hip_shape_cast_closest / b2hip_shape_distance_closest / b2hip_query_shapes_within).
+// b2hip_query_shapes / b2hip_shape_cast_closest / b2hip_shape_distance_closest / b2hip_query_shapes_within /
+// b2hip_ray_cast_all / b2hip_ray_cast_any).
 //
 // Everything is read from the world's device state: the fat AABBs, the proxies' filters and shapes, the bodies' transforms,
 // and the hashed grid of b2d_kernels_broadphase.h, rebuilt from every proxy's box just before (gridRebuildNow). One WAVE per
@@ -10,7 +11,8 @@
 //
 // Determinism: the grid's order inside a bucket depends on arrival, so nothing here depends on it. Box, point and shape
 // queries sort each query's items by fixture id (k_query_sort, k_query_compact_big); rays and shape casts keep the smallest
-// (fraction bits, fixture) key, a total order; the closest distance keeps the smallest (distance bits, fixture) key.
+// (fraction bits, fixture) key, a total order; the closest distance keeps the smallest (distance bits, fixture) key; the
+// all-hit rays sort each ray's (fraction bits, fixture) keys (k_query_sort_keys, k_query_sort_keys_big).
 #ifndef B2D_KERNELS_QUERY_H
 #define B2D_KERNELS_QUERY_H
 
@@ -303,17 +305,18 @@ __global__ __launch_bounds__(256) void k_query_ranges_fill(DW W, const QueryPose
 }
 
 // One workgroup per query: its items sorted ascending in LDS (bitonic network over the next power of two, padded with
-// INT_MAX). Lists longer than QUERY_SORT_MAX are left to k_query_mark / k_query_compact_big.
-__global__ __launch_bounds__(QUERY_SORT_THREADS) void k_query_sort(const int* offsets, int n, int* items)
+// `pad`, the largest value). Lists longer than QUERY_SORT_MAX are left to k_query_mark / k_query_compact_big (fixture ids)
+// or k_query_sort_keys_big (ray keys).
+template <typename T>
+__device__ __forceinline__ void querySortLists(const int* offsets, int n, T* items, T pad, T* s)
 {
-	__shared__ int s[QUERY_SORT_MAX];
 	for (int i = blockIdx.x; i < n; i += gridDim.x)
 	{
 		const int at = offsets[i], len = offsets[i + 1] - at;
 		if (len <= 1 || len > QUERY_SORT_MAX) continue;
 		int size = 2;
 		while (size < len) size <<= 1;
-		for (int k = threadIdx.x; k < size; k += blockDim.x) s[k] = k < len ? items[at + k] : 0x7fffffff;
+		for (int k = threadIdx.x; k < size; k += blockDim.x) s[k] = k < len ? items[at + k] : pad;
 		__syncthreads();
 		for (int span = 2; span <= size; span <<= 1)
 		{
@@ -324,7 +327,7 @@ __global__ __launch_bounds__(QUERY_SORT_THREADS) void k_query_sort(const int* of
 					const int other = k ^ j;
 					if (other > k)
 					{
-						const int x = s[k], y = s[other];
+						const T x = s[k], y = s[other];
 						const bool up = (k & span) == 0;
 						if (up ? x > y : x < y)
 						{
@@ -339,6 +342,48 @@ __global__ __launch_bounds__(QUERY_SORT_THREADS) void k_query_sort(const int* of
 		for (int k = threadIdx.x; k < len; k += blockDim.x) items[at + k] = s[k];
 		__syncthreads();
 	}
+}
+__global__ __launch_bounds__(QUERY_SORT_THREADS) void k_query_sort(const int* offsets, int n, int* items)
+{
+	__shared__ int s[QUERY_SORT_MAX];
+	querySortLists<int>(offsets, n, items, 0x7fffffff, s);
+}
+// the (fraction bits, fixture id) keys of b2hip_ray_cast_all: 32 KB of LDS
+__global__ __launch_bounds__(QUERY_SORT_THREADS) void k_query_sort_keys(const int* offsets, int n, unsigned long long* keys)
+{
+	__shared__ unsigned long long s[QUERY_SORT_MAX];
+	querySortLists<unsigned long long>(offsets, n, keys, ~0ull, s);
+}
+
+// A ray with more than QUERY_SORT_MAX hits: the same network over global memory from ONE workgroup (its barrier orders the
+// rounds), in `work` (size = the next power of two >= len, padded with ~0), and back. One launch per such ray, one after
+// the other from the host: correct, and the slow case of b2hip_ray_cast_all (len = 8192: 91 rounds of 4 exchanges a thread).
+__global__ __launch_bounds__(1024) void k_query_sort_keys_big(unsigned long long* keys, int len, unsigned long long* work, int size)
+{
+	for (int k = threadIdx.x; k < size; k += blockDim.x) work[k] = k < len ? keys[k] : ~0ull;
+	__syncthreads();
+	for (int span = 2; span <= size; span <<= 1)
+	{
+		for (int j = span >> 1; j > 0; j >>= 1)
+		{
+			for (int k = threadIdx.x; k < size; k += blockDim.x)
+			{
+				const int other = k ^ j;
+				if (other > k)
+				{
+					const unsigned long long x = work[k], y = work[other];
+					const bool up = (k & span) == 0;
+					if (up ? x > y : x < y)
+					{
+						work[k] = y;
+						work[other] = x;
+					}
+				}
+			}
+			__syncthreads();
+		}
+	}
+	for (int k = threadIdx.x; k < len; k += blockDim.x) keys[k] = work[k];
 }
 
 // A query with more than QUERY_SORT_MAX items (a box over much of the world): its fixture ids - distinct - are marked in a
@@ -399,6 +444,25 @@ __device__ __forceinline__ unsigned long long waveMinU64(unsigned long long v)
 		v = o < v ? o : v;
 	}
 	return v;
+}
+
+// the record of a hit of fixture q by the ray p1 -> p2: the shape's cast once more (fraction, -0.0 included, and normal)
+__device__ __forceinline__ b2hip_ray_hit queryRayRecord(const DW& W, int q, V2 p1, V2 p2)
+{
+	const int body = W.p_body[q];
+	RayHit hit;
+	(void)b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, body), p1, p2, 1.0f, &hit);
+	const float f = hit.fraction;
+	b2hip_ray_hit o;
+	o.fixture = q;
+	o.body = body;
+	o.point_x = (1.0f - f) * p1.x + f * p2.x;
+	o.point_y = (1.0f - f) * p1.y + f * p2.y;
+	o.normal_x = hit.normal.x;
+	o.normal_y = hit.normal.y;
+	o.fraction = f;
+	o.pad = 0;
+	return o;
 }
 
 __global__ __launch_bounds__(256) void k_query_rays(DW W, const float4* rays, int n, uint32_t mask, int sensors, b2hip_ray_hit* out)
@@ -476,23 +540,153 @@ __global__ __launch_bounds__(256) void k_query_rays(DW W, const float4* rays, in
 			o.point_x = o.point_y = o.normal_x = o.normal_y = 0.0f;
 			o.fraction = 1.0f;
 			o.pad = 0;
-			if (best != ~0ull)
-			{
-				const int q = (int)(uint32_t)best;
-				const int body = W.p_body[q];
-				RayHit hit;
-				(void)b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, body), p1, p2, 1.0f, &hit); // (the kept hit again: its normal)
-				const float f = hit.fraction;
-				o.fixture = q;
-				o.body = body;
-				o.point_x = (1.0f - f) * p1.x + f * p2.x;
-				o.point_y = (1.0f - f) * p1.y + f * p2.y;
-				o.normal_x = hit.normal.x;
-				o.normal_y = hit.normal.y;
-				o.fraction = f;
-			}
+			if (best != ~0ull) o = queryRayRecord(W, (int)(uint32_t)best, p1, p2); // (the kept hit again: its normal)
 			out[i] = o;
 		}
+	}
+}
+
+// Every hit of a ray (b2hip_ray_cast_all) and whether there is one (b2hip_ray_cast_any), one WAVE per ray, walked and culled
+// as k_query_rays does (the same expressions: a piece's t1 is the next piece's t0 to the bit). MODE QUERY_RAY_COUNT:
+// counts[i] = hits of ray i; QUERY_RAY_FILL: their keys (bits of fraction + 0.0f) << 32 | fixture id, unsorted, at
+// keys[offsets[i] ...]; QUERY_RAY_ANY: any[i] = 1 when something is hit.
+// Once only: the windows of successive pieces overlap (gridWindow grows a piece's box by half the grid limit), so a grid-sized
+// proxy is met in several pieces. Piece k accepts a hit only when t0 <= fraction + 0.0f < t1, the last piece up to and
+// including 1: fractions lie in [0, 1] and the pieces' [t0, t1) tile it, so exactly one piece accepts; and that piece meets
+// the proxy - the hit point lies in the piece's box and in the proxy's fat box, so the proxy's centre is in the piece's
+// window (k_query_rays' invariant: after piece k every hit up to t1 has been seen). The rule looks at the fraction alone,
+// never at the order inside a bucket. Large proxies are visited once and accept every hit. A walk the grid refuses (more than
+// QUERY_WINDOW_MAX pieces, a coordinate beyond QUERY_COORD_MAX, a piece's box grown past it) starts over as a scan of every
+// proxy, which also meets each once. The count and the fill pass take the same decisions from the same inputs.
+// Any hit: the same walk with no key kept; once a ballot holds a hit the remaining candidates of that visit are skipped and
+// the walk leaves. It equals `the closest hit exists`: both walks only stop early on a hit.
+#define QUERY_RAY_COUNT 0
+#define QUERY_RAY_FILL 1
+#define QUERY_RAY_ANY 2
+
+template <int MODE>
+__device__ __forceinline__ void queryRayHitsWave(DW W, const float4* rays, int n, uint32_t mask, int sensors, int* counts, const int* offsets,
+                                                 unsigned long long* keys, uint8_t* any)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	const int nWaves = (int)((gridDim.x * blockDim.x) >> 6);
+	for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nWaves)
+	{
+		const float4 r = rays[i];
+		const V2 p1 = v2(r.x, r.y), p2 = v2(r.z, r.w);
+		const V2 d = p2 - p1;
+		int found = 0;
+		const bool finite = isfinite(r.x) && isfinite(r.y) && isfinite(r.z) && isfinite(r.w);
+		if (finite && (d.x != 0.0f || d.y != 0.0f))
+		{
+			const float mag = fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fmaxf(fabsf(r.z), fabsf(r.w)));
+			const float eps = 1.0e-3f + 1.0e-5f * mag;
+			const float len = sqrtf(d.x * d.x + d.y * d.y);
+			const V2 u = v2(d.x / len, d.y / len);
+			const V2 perp = v2(-u.y, u.x), aperp = v2(fabsf(perp.x), fabsf(perp.y));
+			const V2 slo = v2(fminf(p1.x, p2.x) - eps, fminf(p1.y, p2.y) - eps);
+			const V2 shi = v2(fmaxf(p1.x, p2.x) + eps, fmaxf(p1.y, p2.y) + eps);
+			const int at = MODE == QUERY_RAY_FILL ? offsets[i] : 0, end = MODE == QUERY_RAY_FILL ? offsets[i + 1] : 0;
+			float t0 = 0.0f, t1 = 1.0f; // a hit counts when t0 <= fraction + 0.0f < t1 - or <= t1 when `closed`
+			bool closed = true;
+			auto visit = [&](bool valid, int q, float4 fat)
+			{
+				bool cand = valid && !(MODE == QUERY_RAY_ANY && found > 0);
+				cand = cand && !(fat.x > shi.x || fat.y > shi.y || slo.x > fat.z || slo.y > fat.w);
+				if (cand)
+				{
+					const V2 c = v2(0.5f * (fat.x + fat.z), 0.5f * (fat.y + fat.w));
+					const V2 h = v2(0.5f * (fat.z - fat.x) + eps, 0.5f * (fat.w - fat.y) + eps);
+					const V2 rel = p1 - c;
+					cand = fabsf(perp.x * rel.x + perp.y * rel.y) - (aperp.x * h.x + aperp.y * h.y) <= 0.0f;
+				}
+				if (cand) cand = queryFilterPasses(W, q, mask, sensors);
+				bool hit = false;
+				float f = 0.0f;
+				if (cand)
+				{
+					RayHit rh;
+					if (b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), p1, p2, 1.0f, &rh))
+					{
+						f = rh.fraction + 0.0f; // (a -0.0 enters as +0.0, as in k_query_rays)
+						hit = MODE == QUERY_RAY_ANY || (f >= t0 && (f < t1 || closed));
+					}
+				}
+				const unsigned long long m = __ballot(hit);
+				if (MODE == QUERY_RAY_FILL && hit)
+				{
+					const int k = at + found + (int)__popcll(m & ((1ull << lane) - 1ull));
+					if (k < end) keys[k] = ((unsigned long long)__float_as_uint(f) << 32) | (uint32_t)q;
+				}
+				found += (int)__popcll(m);
+			};
+			const float cell = gridCell(W);
+			const float pieces = ceilf(len / cell);
+			bool all = !(pieces <= (float)QUERY_WINDOW_MAX) || !(mag <= QUERY_COORD_MAX);
+			if (!all)
+			{
+				queryVisitLarge(W, lane, visit);
+				const int np = pieces < 1.0f ? 1 : (int)pieces;
+				for (int k = 0; k < np && !(MODE == QUERY_RAY_ANY && found > 0); ++k)
+				{
+					t0 = (float)k / (float)np;
+					t1 = k + 1 == np ? 1.0f : (float)(k + 1) / (float)np;
+					closed = k + 1 == np;
+					const V2 a = p1 + t0 * d, b = k + 1 == np ? p2 : p1 + t1 * d;
+					const float4 box = make_float4(fminf(a.x, b.x) - eps, fminf(a.y, b.y) - eps, fmaxf(a.x, b.x) + eps, fmaxf(a.y, b.y) + eps);
+					if (!queryVisitGrid(W, lane, box, visit))
+					{
+						all = true;
+						break;
+					}
+				}
+			}
+			if (all)
+			{
+				if (MODE != QUERY_RAY_ANY) found = 0; // (the scan meets every proxy once: what the walk gathered is gathered again)
+				t0 = 0.0f;
+				t1 = 1.0f;
+				closed = true;
+				queryVisitAll(W, lane, visit);
+			}
+		}
+		if (lane == 0)
+		{
+			if (MODE == QUERY_RAY_COUNT) counts[i] = found;
+			if (MODE == QUERY_RAY_ANY) any[i] = found > 0 ? 1 : 0;
+		}
+	}
+}
+
+__global__ __launch_bounds__(256) void k_query_rays_all_count(DW W, const float4* rays, int n, uint32_t mask, int sensors, int* counts)
+{
+	queryRayHitsWave<QUERY_RAY_COUNT>(W, rays, n, mask, sensors, counts, nullptr, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void k_query_rays_all_fill(DW W, const float4* rays, int n, uint32_t mask, int sensors, const int* offsets,
+                                                             unsigned long long* keys)
+{
+	queryRayHitsWave<QUERY_RAY_FILL>(W, rays, n, mask, sensors, nullptr, offsets, keys, nullptr);
+}
+__global__ __launch_bounds__(256) void k_query_rays_any(DW W, const float4* rays, int n, uint32_t mask, int sensors, uint8_t* any)
+{
+	queryRayHitsWave<QUERY_RAY_ANY>(W, rays, n, mask, sensors, nullptr, nullptr, nullptr, any);
+}
+
+// The records of b2hip_ray_cast_all, after the sort: one thread per key. Key k belongs to the last ray i with
+// offsets[i] <= k (as k_query_range_eval finds its query); its fixture is cast again and the record written out whole.
+__global__ __launch_bounds__(256) void k_query_rays_all_eval(DW W, const float4* rays, int n, const int* offsets, const unsigned long long* keys,
+                                                             int nItems, b2hip_ray_hit* out)
+{
+	for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < nItems; k += (int)(gridDim.x * blockDim.x))
+	{
+		int lo = 0, hi = n; // (offsets[lo] <= k < offsets[hi])
+		while (hi - lo > 1)
+		{
+			const int mid = (lo + hi) >> 1;
+			if (offsets[mid] <= k) lo = mid; else hi = mid;
+		}
+		const float4 r = rays[lo];
+		out[k] = queryRayRecord(W, (int)(uint32_t)keys[k], v2(r.x, r.y), v2(r.z, r.w));
 	}
 }
 

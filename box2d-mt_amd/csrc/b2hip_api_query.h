@@ -1,4 +1,5 @@
-// b2hip_api_query.h - batched AABB, point, shape-overlap, closest-ray, closest-shape-cast and distance queries between steps
+// b2hip_api_query.h - batched AABB, point, shape-overlap, ray (closest, all hits, any hit), closest-shape-cast and distance
+// queries between steps
 // (include/b2hip.h; kernels: b2d_kernels_query.h).
 //
 // What a query sees: the edits made since the last step are uploaded first (flushEdits - what the next step's first call
@@ -270,6 +271,14 @@ int b2hip_query_points(b2hip_world* w, int n, const float* points2n, const b2hip
 	return queryBoxes(w, what, n, points2n, QUERY_POINT, nullptr, nullptr, f, cap, offsets, items);
 }
 
+// the rays of a batch into the pinned buffer (at least `atLeast` bytes of it) and on to the device, a fresh grid
+static int queryRaysBegin(b2hip_world* w, int n, const float* rays4n, size_t atLeast, bool offsets)
+{
+	if (int rc = queryPinned(w, std::max((size_t)n * sizeof(float4), atLeast))) return rc;
+	memcpy(w->qPinned, rays4n, (size_t)n * sizeof(float4));
+	return queryBegin(w, n, offsets);
+}
+
 int b2hip_ray_cast_closest(b2hip_world* w, int n, const float* rays4n, const b2hip_query_filter* f, b2hip_ray_hit* out)
 {
 	const char* what = "b2hip_ray_cast_closest";
@@ -280,10 +289,7 @@ int b2hip_ray_cast_closest(b2hip_world* w, int n, const float* rays4n, const b2h
 	if (n == 0) return B2HIP_OK;
 	const uint32_t mask = f ? (uint32_t)f->mask : 0xffffu;
 	const int sensors = f ? (f->include_sensors != 0) : 1;
-	int rc = queryPinned(w, (size_t)n * std::max(sizeof(float4), sizeof(b2hip_ray_hit)));
-	if (rc) return rc;
-	memcpy(w->qPinned, rays4n, (size_t)n * sizeof(float4));
-	rc = queryBegin(w, n, false);
+	int rc = queryRaysBegin(w, n, rays4n, (size_t)n * sizeof(b2hip_ray_hit), false);
 	if (rc) return rc;
 	hipStream_t s = w->stream;
 	DW& d = w->dw;
@@ -306,6 +312,105 @@ int b2hip_ray_cast_closest(b2hip_world* w, int n, const float* rays4n, const b2h
 	HIP_TRY(hipStreamSynchronize(s));
 	if ((rc = queryScanAborted(w, what))) return rc;
 	memcpy(out, w->qPinned, (size_t)n * sizeof(b2hip_ray_hit));
+	return B2HIP_OK;
+}
+
+// Every hit of every ray: a count pass, a scan, a fill pass of (fraction bits, fixture id) keys, the sort of each ray's keys
+// (in LDS; a ray with more than QUERY_SORT_MAX hits by one launch of its own over global memory), and the records of the
+// first min(total, cap) keys.
+int b2hip_ray_cast_all(b2hip_world* w, int n, const float* rays4n, const b2hip_query_filter* f, int cap, int32_t* offsets, b2hip_ray_hit* hits)
+{
+	const char* what = "b2hip_ray_cast_all";
+	if (int rc = queryListArgs(what, n, rays4n, cap, offsets, hits)) return rc;
+	if (int rc = queryUsable(w, what)) return rc;
+	DEVICE_GUARD(w);
+	const uint32_t mask = f ? (uint32_t)f->mask : 0xffffu;
+	const int sensors = f ? (f->include_sensors != 0) : 1;
+	offsets[0] = 0;
+	if (n == 0) return 0;
+	const size_t offsetBytes = ((size_t)n + 1) * sizeof(int);
+	int rc = queryRaysBegin(w, n, rays4n, offsetBytes, true);
+	if (rc) return rc;
+	hipStream_t s = w->stream;
+	DW& d = w->dw;
+	const float4* rays = (const float4*)w->qIn.p;
+	const int waveBlocks = gridFor((size_t)n * 64, 256, 8192); // (one wave per ray)
+	if (d.nProxies == 0) HIP_TRY(hipMemsetAsync(w->qOffsets.p, 0, offsetBytes, s));
+	else
+	{
+		LAUNCH(w, k_query_rays_all_count, waveBlocks, 256, d, rays, n, mask, sensors, w->qCounts.p);
+		deviceExclusiveScan<int>(s, w->qCounts.p, w->qOffsets.p, w->qScanWork.p, w->qScan, w->qWords.p, n);
+	}
+	int* hOff = (int*)w->qPinned;
+	HIP_TRY(hipMemcpyAsync(hOff, w->qOffsets.p, offsetBytes, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if ((rc = queryScanAborted(w, what))) return rc;
+	memcpy(offsets, hOff, offsetBytes);
+	const int total = offsets[n];
+	if (total < 0) return setError(B2HIP_ERR_CAPACITY, std::string(what) + ": more than 2^31 hits");
+	const int copy = std::min(total, cap);
+	if (total > 0)
+	{
+		rc = w->qKeys.ensure((size_t)total, s, false, false);
+		if (rc) return rc;
+		const int* offs = (const int*)w->qOffsets.p;
+		LAUNCH(w, k_query_rays_all_fill, waveBlocks, 256, d, rays, n, mask, sensors, offs, w->qKeys.p);
+		LAUNCH(w, k_query_sort_keys, gridFor((size_t)n, 1, 16384), QUERY_SORT_THREADS, offs, n, w->qKeys.p);
+		for (int i = 0; i < n; ++i)
+		{
+			const int len = offsets[i + 1] - offsets[i];
+			if (len <= QUERY_SORT_MAX) continue;
+			if (len > (1 << 30)) return setError(B2HIP_ERR_CAPACITY, std::string(what) + ": more than 2^30 hits of one ray");
+			size_t size = 2 * (size_t)QUERY_SORT_MAX;
+			while (size < (size_t)len) size *= 2;
+			rc = w->qKeysWork.ensure(size, s, false, false);
+			if (rc) return rc;
+			LAUNCH(w, k_query_sort_keys_big, 1, 1024, w->qKeys.p + offsets[i], len, w->qKeysWork.p, (int)size);
+		}
+		if (copy > 0)
+		{
+			rc = w->qHits.ensure((size_t)copy, s, false, false);
+			if (rc) return rc;
+			LAUNCH(w, k_query_rays_all_eval, gridFor((size_t)copy), 256, d, rays, n, offs, (const unsigned long long*)w->qKeys.p, copy, w->qHits.p);
+		}
+	}
+	rc = queryEnd(w);
+	if (rc) return rc;
+	if ((rc = queryPinned(w, (size_t)copy * sizeof(b2hip_ray_hit)))) return rc; // (the offsets have left it)
+	if (copy > 0) HIP_TRY(hipMemcpyAsync(w->qPinned, w->qHits.p, (size_t)copy * sizeof(b2hip_ray_hit), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if (copy > 0) memcpy(hits, w->qPinned, (size_t)copy * sizeof(b2hip_ray_hit));
+	return total;
+}
+
+int b2hip_ray_cast_any(b2hip_world* w, int n, const float* rays4n, const b2hip_query_filter* f, uint8_t* out)
+{
+	const char* what = "b2hip_ray_cast_any";
+	if (n < 0 || n > B2HIP_QUERY_MAX) return setError(B2HIP_ERR_INVALID, std::string(what) + ": n must lie in [0, 2^24]");
+	if (!out || (n > 0 && !rays4n)) return setError(B2HIP_ERR_INVALID, std::string(what) + ": null input or output");
+	if (int rc = queryUsable(w, what)) return rc;
+	DEVICE_GUARD(w);
+	if (n == 0) return B2HIP_OK;
+	const uint32_t mask = f ? (uint32_t)f->mask : 0xffffu;
+	const int sensors = f ? (f->include_sensors != 0) : 1;
+	int rc = queryRaysBegin(w, n, rays4n, 0, false);
+	if (rc) return rc;
+	hipStream_t s = w->stream;
+	DW& d = w->dw;
+	if (d.nProxies == 0)
+	{
+		memset(out, 0, (size_t)n);
+		return B2HIP_OK;
+	}
+	rc = w->qAny.ensure((size_t)n, s, false, false);
+	if (rc) return rc;
+	LAUNCH(w, k_query_rays_any, gridFor((size_t)n * 64, 256, 8192), 256, d, (const float4*)w->qIn.p, n, mask, sensors, w->qAny.p);
+	rc = queryEnd(w);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(w->qPinned, w->qAny.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if ((rc = queryScanAborted(w, what))) return rc;
+	memcpy(out, w->qPinned, (size_t)n);
 	return B2HIP_OK;
 }
 

@@ -198,6 +198,8 @@ struct b2hip_world
 	DevArray<int> qCounts, qOffsets, qItems, qFlags, qScanWork, qScanWords, qWords;
 	DevArray<b2hip_ray_hit> qHits;
 	DevArray<b2hip_distance_hit> qDistances; // the records of the distance queries
+	DevArray<unsigned long long> qKeys, qKeysWork; // b2hip_ray_cast_all: the hits' (fraction bits, fixture id) keys; the long-list sort's room
+	DevArray<uint8_t> qAny;                  // b2hip_ray_cast_any
 	DevArray<QueryPose> qPoses; // shape queries and casts: pose, shape index, translation per query
 	DevArray<ShapeRec> qShapes; // ... and the call's query shapes (the GJK proxies point into this table)
 	ScanFlags qScan;

@@ -463,6 +463,46 @@ int b2h_raycast_closest(b2h_world* h, float x1, float y1, float x2, float y2, fl
 	return 1;
 }
 
+// b2World::RayCast with a callback that reports EVERY fixture the ray crosses: it returns -1 for the fixtures a
+// b2hip_query_filter would not pass ((categoryBits & mask) == 0, or a sensor while `sensors` is 0), records the rows of the
+// others in the out7 layout of b2h_raycast_closest and returns 1 (the ray is not clipped). Returns the number of hits and
+// writes the first `cap` rows, in the order the tree visits them. Public Box2D API only: every backend has it.
+namespace
+{
+struct AllPassingHits : b2RayCastCallback
+{
+	b2h_world* h = nullptr;
+	int mask = 0xFFFF, sensors = 1, cap = 0, count = 0;
+	float* out = nullptr;
+	float32 ReportFixture(b2Fixture* f, const b2Vec2& p, const b2Vec2& n, float32 fr) override
+	{
+		if ((f->GetFilterData().categoryBits & mask) == 0 || (!sensors && f->IsSensor())) return -1.0f;
+		if (count < cap)
+		{
+			float* o = out + 7 * (size_t)count;
+			o[0] = (float)h->bodyIndex[f->GetBody()];
+			o[1] = (float)FixtureIndexInBody(f);
+			o[2] = p.x; o[3] = p.y;
+			o[4] = n.x; o[5] = n.y;
+			o[6] = fr;
+		}
+		++count;
+		return 1.0f;
+	}
+};
+}
+int b2h_raycast_all_filtered(b2h_world* h, float x1, float y1, float x2, float y2, int mask, int sensors, int cap, float* out7n)
+{
+	AllPassingHits cb;
+	cb.h = h;
+	cb.mask = mask;
+	cb.sensors = sensors;
+	cb.cap = cap;
+	cb.out = out7n;
+	h->world->RayCast(&cb, b2Vec2(x1, y1), b2Vec2(x2, y2));
+	return cb.count;
+}
+
 #if defined(B2H_BACKEND_AMD)
 // Device fixture id -> (body, fixture index in body) in out2[2 * id]; a chain's children share their fixture's row. Ids
 // nobody owns (destroyed, inactive) read -1. Returns the number of device fixture ids (the batched device queries report

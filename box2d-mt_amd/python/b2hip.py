@@ -205,6 +205,8 @@ def _configure(L, optional_ok=False):
         "b2hip_query_aabbs": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_query_points": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_ray_cast_closest": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_void_p],
+        "b2hip_ray_cast_all": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_ray_cast_any": [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_void_p],
         "b2hip_query_shapes": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int,
                                C.c_void_p, C.c_void_p],
         "b2hip_shape_cast_closest": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter),
@@ -559,7 +561,7 @@ class World:
         _check(self.L.b2hip_get_profile(self.p, ms))
         return list(ms)
 
-    # ---- batched queries on the device (include/b2hip.h: b2hip_query_aabbs, b2hip_query_points, b2hip_ray_cast_closest)
+    # ---- batched queries on the device (include/b2hip.h: b2hip_query_aabbs, b2hip_query_points, b2hip_ray_cast_closest / _all / _any)
     @staticmethod
     def _pairs(a, name):
         a = np.ascontiguousarray(a, np.float32)
@@ -593,17 +595,35 @@ class World:
         pts = self._pairs(points, "points")
         return self._query(self.L.b2hip_query_points, pts, len(pts), mask, sensors)
 
-    def ray_cast_closest(self, p1, p2, mask=0xFFFF, sensors=True):
-        """Closest hit of ray i from p1[i] to p2[i]: a RAY_HIT_DTYPE array, fixture = -1 where the ray hits nothing."""
+    def _rays(self, p1, p2, name):
         a, b = self._pairs(p1, "p1"), self._pairs(p2, "p2")
         if a.shape != b.shape:
-            raise ValueError("ray_cast_closest: p1 and p2 differ in shape")
-        rays = np.ascontiguousarray(np.concatenate([a, b], axis=1))
+            raise ValueError("%s: p1 and p2 differ in shape" % name)
+        return np.ascontiguousarray(np.concatenate([a, b], axis=1))
+
+    def ray_cast_closest(self, p1, p2, mask=0xFFFF, sensors=True):
+        """Closest hit of ray i from p1[i] to p2[i]: a RAY_HIT_DTYPE array, fixture = -1 where the ray hits nothing."""
+        rays = self._rays(p1, p2, "ray_cast_closest")
         out = np.zeros(len(rays), RAY_HIT_DTYPE)
         f = QueryFilter(mask, int(bool(sensors)))
         _check(self.L.b2hip_ray_cast_closest(self.p, len(rays), rays.ctypes.data_as(C.c_void_p), C.byref(f),
                                              out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def ray_cast_all(self, p1, p2, mask=0xFFFF, sensors=True):
+        """Every fixture ray i crosses from p1[i] to p2[i]: (offsets[n + 1], hits) with hits[offsets[i]:offsets[i + 1]] the
+        RAY_HIT_DTYPE records of ray i in ascending (fraction, fixture id); the first is ray_cast_closest's."""
+        rays = self._rays(p1, p2, "ray_cast_all")
+        return self._query(self.L.b2hip_ray_cast_all, rays, len(rays), mask, sensors, dtype=RAY_HIT_DTYPE)
+
+    def ray_cast_any(self, p1, p2, mask=0xFFFF, sensors=True):
+        """Whether ray i from p1[i] to p2[i] crosses a fixture: a bool array of n (ray_cast_closest(...)["fixture"] >= 0)."""
+        rays = self._rays(p1, p2, "ray_cast_any")
+        out = np.zeros(len(rays), np.uint8)
+        f = QueryFilter(mask, int(bool(sensors)))
+        _check(self.L.b2hip_ray_cast_any(self.p, len(rays), rays.ctypes.data_as(C.c_void_p), C.byref(f),
+                                         out.ctypes.data_as(C.c_void_p)))
+        return out.astype(bool)
 
     @staticmethod
     def _shape_table(shapes, n, shape_index):

@@ -880,6 +880,44 @@ int b2hip_shape_distance_closest(b2hip_world* w, int n_shapes, const b2hip_shape
 int b2hip_query_shapes_within(b2hip_world* w, int n_shapes, const b2hip_shape* shapes, int n, const b2hip_shape_range* ranges,
                               const b2hip_query_filter* f, int cap, int32_t* offsets, b2hip_distance_hit* hits);
 
+/* ---- Batched all-hit and any-hit ray casts on the device (same file, same kernels) ----------------------------------------
+ * Every fixture a ray crosses (b2hip_ray_cast_all: multi-return lidar, projectiles that penetrate, what lies between A and
+ * B) or whether it crosses one at all (b2hip_ray_cast_any: line of sight, one byte per ray), for many rays in one blocking
+ * call; on the same terms as the blocks above: the world of b2hip_get_fat_aabbs / b2hip_get_body_states at the call,
+ * pending edits uploaded first, the filter and the ids as above, the same bytes run after run, a queried world stepping bit
+ * for bit like one that is not. Each call runs on the world's stream and returns when the results are on the host.
+ *
+ * rays: 4n floats (p1.x, p1.y, p2.x, p2.y), as b2hip_ray_cast_closest takes them.
+ * Hit set of ray i: every live proxy that passes the filter and whose shape's ray cast (b2Shape::RayCast at the body's
+ *   transform with p1, p2 and maxFraction = 1) returns true: the set b2World::RayCast reports to a callback that returns 1
+ *   for the fixtures the filter passes and -1 for the others. Each proxy appears once; a chain's child is a fixture id of
+ *   its own. A ray that starts inside a polygon does not hit it (b2PolygonShape::RayCast).
+ * Record: a b2hip_ray_hit exactly as b2hip_ray_cast_closest fills it - fraction and normal from the shape's ray cast, point
+ *   = (1 - fraction) * p1 + fraction * p2, pad = 0.
+ * Order: ascending by (bits of fraction + 0.0f, fixture id): a fraction of -0.0 (a ray that starts on an edge or a circle)
+ *   sorts as +0.0 and is reported as it is, and ties go to the LOWER fixture id. So hits[offsets[i]] is bit for bit what
+ *   b2hip_ray_cast_closest returns for ray i.
+ * b2hip_ray_cast_all: offsets (n + 1) are always complete, hits receives the first min(total, cap) records, the total is
+ *   returned (or a b2hip_status): when it exceeds cap, call again with cap = the total - exactly as b2hip_query_aabbs. A
+ *   total above 2^31, or more than 2^30 hits of one ray: B2HIP_ERR_CAPACITY.
+ * b2hip_ray_cast_any: out[i] = 1 when the hit set of ray i is not empty, else 0; for every input this is
+ *   b2hip_ray_cast_closest(...)[i].fixture >= 0. Returns B2HIP_OK or a b2hip_status.
+ * Invalid rays: a zero-length ray or a coordinate that is not finite gives an empty list / 0.
+ * Argument errors, refused with B2HIP_ERR_INVALID before any device work and before the world is looked at: n outside
+ *   [0, 2^24], a NULL input or output, a negative cap. Then: a NULL world, or a call inside an open step,
+ *   B2HIP_ERR_INVALID; a sharded world (b2hip_set_shard with more than one rank, b2hip_shard_spatial)
+ *   B2HIP_ERR_UNSUPPORTED.
+ * Cost: one wave per ray over the broad-phase grid, in pieces a cell long. A ray of more than 4096 pieces, or a coordinate
+ *   beyond 1e8 in magnitude, tests every proxy of the world from its one wave instead (10^6 candidates on a 10^6-body
+ *   world) - twice in the all-hit call, which counts and then fills. The all-hit call walks the WHOLE ray where the closest
+ *   call stops at the first piece that holds a hit, casts every reported fixture once more for its record, and sorts each
+ *   ray's list in LDS; a ray with more than 4096 hits is sorted in global memory by one workgroup, one launch per such ray,
+ *   one after the other from the host: correct, and slow. The any-hit call stops at the first piece that holds a hit and
+ *   copies one byte per ray back. */
+int b2hip_ray_cast_all(b2hip_world* w, int n, const float* rays4n, const b2hip_query_filter* f, int cap, int32_t* offsets,
+                       b2hip_ray_hit* hits);
+int b2hip_ray_cast_any(b2hip_world* w, int n, const float* rays4n, const b2hip_query_filter* f, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,12 +1,15 @@
-"""Batched device queries (include/b2hip.h: b2hip_query_aabbs / b2hip_query_points / b2hip_ray_cast_closest) on the two
-BASELINE worlds bench.py settles, against the drop-in's host path on the same world.
+"""Batched device queries (include/b2hip.h: b2hip_query_aabbs / b2hip_query_points / b2hip_ray_cast_closest / b2hip_ray_cast_all /
+b2hip_ray_cast_any) on the two BASELINE worlds bench.py settles, against the drop-in's host path on the same world.
 
   python tools/gpu_queries.py queries [--out FILE]    call times of 10^5 rays (1-20 m), 10^5 boxes (half extents 0.25-3 m)
                                                       and 10^5 points on the settled config 5 field (10^6 bodies) and the
                                                       settled config 3 Tumbler; the fixed cost of a call (edits, the grid
                                                       rebuild, one query) apart; the drop-in: the first b2World::QueryAABB
                                                       after a step (its shadow-tree sync) and 1 000 rays / boxes through
-                                                      b2World::RayCast / QueryAABB, per query
+                                                      b2World::RayCast / QueryAABB, per query. The all-hit and any-hit
+                                                      calls take the same rays as the closest call, in the same run: their
+                                                      times against it, beside the spread of its repeated runs (the noise),
+                                                      and the drop-in's RayCast with an all-hits callback on 1 000 of them
   python tools/gpu_queries.py steps --harness LIB     ms per b2hip_step of both settled worlds (one JSON line), for an
                                                       A/B of two builds in separate processes
   python tools/gpu_queries.py kernels DIR             the k_query_* kernel times of a separate
@@ -14,6 +17,7 @@ BASELINE worlds bench.py settles, against the drop-in's host path on the same wo
 tools/gpu_queries.sh runs the whole sequence, every GPU step under its own time limit.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -75,6 +79,16 @@ def run_queries(args):
         rec["points_call_ms"], _ = timed(lambda: dw.query_points(pts), args.reps)
         hits = dw.ray_cast_closest(p1, p2)
         rec["ray_hits"] = int((hits["fixture"] >= 0).sum())
+        # all hits / any hit on the closest call's rays; the closest call once more around them, its runs' spread = the noise
+        rec["rays_all_call_ms"], _ = timed(lambda: dw.ray_cast_all(p1, p2), args.reps)
+        rec["rays_any_call_ms"], _ = timed(lambda: dw.ray_cast_any(p1, p2), args.reps)
+        again, ts = timed(lambda: dw.ray_cast_closest(p1, p2), args.reps)
+        rec["rays_call_again_ms"] = again
+        rec["rays_call_spread_ms"] = max(ts) - min(ts)
+        rec["rays_all_over_closest"] = rec["rays_all_call_ms"] / again
+        rec["rays_any_over_closest"] = rec["rays_any_call_ms"] / again
+        rec["ray_all_records"] = int(dw.ray_cast_all(p1, p2)[0][-1])
+        rec["ray_any_true"] = int(dw.ray_cast_any(p1, p2).sum())
         offs, _ = dw.query_aabbs(c - e, c + e)
         rec["aabb_items"] = int(offs[-1])
         if not args.quick:
@@ -88,12 +102,20 @@ def run_queries(args):
             for i in range(k):
                 w.raycast_closest(p1[i], p2[i])
             rec["dropin_ray_us"] = 1e6 * (time.perf_counter() - t0) / k
+            every = w.L.b2h_raycast_all_filtered  # (b2World::RayCast, a callback that returns 1: every fixture crossed)
+            every.argtypes = [C.c_void_p] + [C.c_float] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p]
+            rows = np.zeros((4096, 7), np.float32)
+            sample = np.concatenate([p1[:k], p2[:k]], axis=1).astype(np.float64).tolist()
+            t0 = time.perf_counter()
+            for x1, y1, x2, y2 in sample:
+                every(w.ptr, x1, y1, x2, y2, 0xFFFF, 1, len(rows), rows.ctypes.data_as(C.c_void_p))
+            rec["dropin_ray_all_us"] = 1e6 * (time.perf_counter() - t0) / k
             t0 = time.perf_counter()
             for i in range(k):
                 w.query_aabb(c[i] - e[i], c[i] + e[i])
             rec["dropin_aabb_us"] = 1e6 * (time.perf_counter() - t0) / k
             # per query, the drop-in path = its sync once (spread over the batch) + its per-query time
-            for kind, key in (("ray", "rays_call_ms"), ("aabb", "aabbs_call_ms")):
+            for kind, key in (("ray", "rays_call_ms"), ("ray_all", "rays_all_call_ms"), ("aabb", "aabbs_call_ms")):
                 dev_us = 1000.0 * rec[key] / n
                 host_us = rec["dropin_%s_us" % kind] + 1000.0 * rec["dropin_first_query_after_step_ms"] / n
                 rec["%s_speedup_per_query" % kind] = host_us / dev_us
