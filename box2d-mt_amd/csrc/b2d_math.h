@@ -5,7 +5,7 @@
 // the translation unit is built with -ffp-contract=off and IEEE divide/sqrt, so a lane that walks
 // an island in the reference's order reproduces the reference's floats bit for bit.
 //
-// B2D_HD expands to __host__ __device__ under hipcc; the CPU test shim (tests/host_probe.cpp)
+// B2D_HD expands to __host__ __device__ under hipcc; the CPU test shim (tests/probe/host_probe.cpp)
 // compiles the same header with g++ to pin the math against oracle/_ref without a GPU.
 #ifndef B2D_MATH_H
 #define B2D_MATH_H
@@ -23,7 +23,8 @@
 #endif
 
 // --- tuning constants (Box2D/Common/b2Settings.h:47-174) -------------------------------------
-// (in this header so that the CPU build can check it exhaustively: tests/test_device_math_cpu.py)
+// (in this header so that the CPU build can check it exhaustively: tests/test_device_math_cpu.py; the device build of the
+// same function is held to the integer remainder over the same domain by tests/test_gpu_device_math.py)
 // The block (+ 1) a body takes by its own id: hash(body) mod blocks. The remainder goes by way of a float quotient with BOTH
 // corrections, not through `%`: with a divisor the compiler knows to be small it expands `%` into its 24-bit form, and
 // inside k_block_census that form returned 0xffffff for x = 0xc1f9f3, nb = 11 (a quotient one too large, the remainder - 1,
@@ -301,6 +302,9 @@ static SinCosPair b2dSinCosLarge(float y)
 // fma(-0, pi/2, x) = x, and for |y| < 2^-12 the polynomials round to y and 1 (x^3/6 and x^2/2 are below half an ulp of the
 // results). Every operation is the one b2dSin / b2dCos perform on the same operands; the pair is checked bit for bit
 // against libm's sinf / cosf for ALL 2^32 inputs (tests/test_device_math_cpu.py, exhaustive variant in tools/probe_sincos_all.py).
+// That is the g++ build; the device build - this function, b2dSin, b2dCos and both b2dRot forms as hipcc compiles them - is
+// compared bit for bit with the g++ build over a 1/4099 strided sweep of all 2^32 inputs, twice, and with the reference's
+// recorded vectors (tests/test_gpu_device_math.py through tests/probe/device_probe.hip).
 // The straight line matters on the device: the position solver calls this four times per two-point contact, one wave per
 // SIMD, and with three diverging ranges inlined at every site the loop was 25 KB of code.
 B2D_HD void b2dSinCos(float y, float* sinOut, float* cosOut)

@@ -1221,6 +1221,95 @@ void b2h_probe_shape_cast(int countA, const float* vertsA, float radiusA, const 
 	out7[6] = (float)out.iterations;
 }
 
+// --- one-shape probes: b2Shape::RayCast / TestPoint / ComputeAABB / ComputeMass through the virtual interface.
+// shape20 = {kind, count, child, radius, 16 floats}:
+//   kind 0 circle  : radius, m_p = floats[0..1]
+//   kind 1 edge    : floats[0..9] = FillEdge's layout
+//   kind 2 polygon : Set(count points)
+//   kind 3 box     : SetAsBox(floats[0], floats[1])
+//   kind 4 chain   : CreateChain(count points); the probes address child `child`
+namespace
+{
+struct ProbeShape
+{
+	b2CircleShape circle;
+	b2EdgeShape edge;
+	b2PolygonShape polygon;
+	b2ChainShape chain;
+	const b2Shape* shape;
+	int32 child;
+
+	explicit ProbeShape(const float* d) : shape(NULL), child(0)
+	{
+		const int kind = (int)d[0], count = (int)d[1];
+		const float* f = d + 4;
+		if (kind == 0)
+		{
+			circle.m_p.Set(f[0], f[1]);
+			circle.m_radius = d[3];
+			shape = &circle;
+		}
+		else if (kind == 1)
+		{
+			FillEdge(edge, f);
+			shape = &edge;
+		}
+		else if (kind == 2 || kind == 3)
+		{
+			FillPolygon(polygon, count, f, kind == 3);
+			shape = &polygon;
+		}
+		else
+		{
+			b2Vec2 v[b2_maxPolygonVertices];
+			for (int i = 0; i < count; ++i) v[i].Set(f[2 * i], f[2 * i + 1]);
+			chain.CreateChain(v, count);
+			shape = &chain;
+			child = (int32)d[2];
+		}
+	}
+};
+}
+
+// ray5 = {p1.x, p1.y, p2.x, p2.y, maxFraction}; out3 = {fraction, normal.x, normal.y}; returns 1 on a hit
+int b2h_probe_shape_raycast(const float* shape20, const float* xf, const float* ray5, float* out3)
+{
+	ProbeShape s(shape20);
+	b2RayCastInput in;
+	in.p1.Set(ray5[0], ray5[1]);
+	in.p2.Set(ray5[2], ray5[3]);
+	in.maxFraction = ray5[4];
+	b2RayCastOutput out;
+	if (!s.shape->RayCast(&out, in, MakeXf(xf), s.child)) return 0;
+	out3[0] = out.fraction; out3[1] = out.normal.x; out3[2] = out.normal.y;
+	return 1;
+}
+
+int b2h_probe_test_point(const float* shape20, const float* xf, float px, float py)
+{
+	ProbeShape s(shape20);
+	return s.shape->TestPoint(MakeXf(xf), b2Vec2(px, py)) ? 1 : 0;
+}
+
+// out4 = {lowerBound.x, lowerBound.y, upperBound.x, upperBound.y}
+void b2h_probe_shape_aabb(const float* shape20, const float* xf, float* out4)
+{
+	ProbeShape s(shape20);
+	b2AABB box;
+	s.shape->ComputeAABB(&box, MakeXf(xf), s.child);
+	out4[0] = box.lowerBound.x; out4[1] = box.lowerBound.y;
+	out4[2] = box.upperBound.x; out4[3] = box.upperBound.y;
+}
+
+// out4 = {mass, center.x, center.y, I}
+void b2h_probe_shape_mass(const float* shape20, float density, float* out4)
+{
+	ProbeShape s(shape20);
+	b2MassData md;
+	s.shape->ComputeMass(&md, density);
+	out4[0] = md.mass; out4[1] = md.center.x; out4[2] = md.center.y; out4[3] = md.I;
+}
+
 // b2AABB::RayCast: out3 = {fraction, normal.x, normal.y}; returns 1 on a hit
 int b2h_probe_aabb_raycast(const float* box4, const float* ray5, float* out3)
 {

@@ -161,6 +161,47 @@ class Harness:
                                C.c_float(radiusB), _fptr(b), C.c_float(t_max), _fptr(out))
         return out
 
+    def shape_cast(self, vertsA, radiusA, xfA, vertsB, radiusB, xfB, travel):
+        """b2ShapeCast on raw vertex proxies, B moving by `travel` -> [hit, point.xy, normal.xy, lambda, iterations]"""
+        va = np.ascontiguousarray(vertsA, np.float32).reshape(-1)
+        vb = np.ascontiguousarray(vertsB, np.float32).reshape(-1)
+        a = np.asarray(xfA, np.float32)
+        b = np.asarray(xfB, np.float32)
+        out = np.zeros(7, np.float32)
+        self.lib.b2h_probe_shape_cast(va.size // 2, _fptr(va), C.c_float(radiusA), _fptr(a), vb.size // 2, _fptr(vb),
+                                      C.c_float(radiusB), _fptr(b), C.c_float(travel[0]), C.c_float(travel[1]), _fptr(out))
+        return out
+
+    # ---- one-shape probes: shape20 = [kind, count, child, radius, 16 floats] (see harness.cpp: ProbeShape) ----
+    def shape_raycast(self, shape20, xf, ray5):
+        """b2Shape::RayCast -> [hit, fraction, normal.xy] (zeros after the flag on a miss)"""
+        s = np.ascontiguousarray(shape20, np.float32)
+        x = np.ascontiguousarray(xf, np.float32)
+        r = np.ascontiguousarray(ray5, np.float32)
+        out = np.zeros(4, np.float32)
+        self.lib.b2h_probe_shape_raycast.restype = C.c_int
+        out[0] = self.lib.b2h_probe_shape_raycast(_fptr(s), _fptr(x), _fptr(r), _fptr(out[1:]))
+        return out
+
+    def test_point(self, shape20, xf, p):
+        s = np.ascontiguousarray(shape20, np.float32)
+        x = np.ascontiguousarray(xf, np.float32)
+        self.lib.b2h_probe_test_point.restype = C.c_int
+        return int(self.lib.b2h_probe_test_point(_fptr(s), _fptr(x), C.c_float(p[0]), C.c_float(p[1])))
+
+    def shape_aabb(self, shape20, xf):
+        s = np.ascontiguousarray(shape20, np.float32)
+        x = np.ascontiguousarray(xf, np.float32)
+        out = np.zeros(4, np.float32)
+        self.lib.b2h_probe_shape_aabb(_fptr(s), _fptr(x), _fptr(out))
+        return out
+
+    def shape_mass(self, shape20, density):
+        s = np.ascontiguousarray(shape20, np.float32)
+        out = np.zeros(4, np.float32)
+        self.lib.b2h_probe_shape_mass(_fptr(s), C.c_float(density), _fptr(out))
+        return out
+
     def sincos(self, angles):
         a = np.ascontiguousarray(angles, np.float32)
         s = np.empty_like(a)

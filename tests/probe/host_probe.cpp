@@ -1,7 +1,7 @@
 // CPU compile of the device math headers (box2d-mt_amd/csrc/b2d_*.h) for bit-level checks against
 // oracle/_ref WITHOUT a GPU.  TEST INFRASTRUCTURE: nothing in the product links this file.
-#include "b2d_solver.h"
-#include "b2d_toi.h"
+// (probe_cases.h holds one vector of each family; device_probe.hip runs the same cases one vector per GPU thread)
+#include "probe_cases.h"
 #include <math.h>
 
 extern "C"
@@ -14,6 +14,12 @@ void probe_sincos(int n, const float* a, float* s, float* c)
 		s[i] = b2dSin(a[i]);
 		c[i] = b2dCos(a[i]);
 	}
+}
+
+// all five entry points per angle (caseSinCos): out8[n][8]
+void probe_sincos_all(int n, const float* a, float* out8)
+{
+	for (int i = 0; i < n; ++i) caseSinCos(a[i], out8 + 8 * (size_t)i);
 }
 
 // exhaustive-ish check against this machine's libm over [lo, hi] bit patterns; returns mismatches
@@ -38,75 +44,49 @@ long probe_sincos_vs_libm(unsigned lo, unsigned hi, unsigned stride)
 // xf = px, py, angle ; out = 16 floats in the harness manifold layout
 void probe_collide(const void* shapeA, const float* xfA, const void* shapeB, const float* xfB, float* out)
 {
-	const ShapeRec* sA = (const ShapeRec*)shapeA;
-	const ShapeRec* sB = (const ShapeRec*)shapeB;
-	Xf a, b;
-	a.p = v2(xfA[0], xfA[1]);
-	a.q = b2dRot(xfA[2]);
-	b.p = v2(xfB[0], xfB[1]);
-	b.q = b2dRot(xfB[2]);
-	Manifold m;
-	memset(&m, 0, sizeof(m));
-	b2dEvaluate(&m, sA, a, sB, b);
-	for (int i = 0; i < 16; ++i) out[i] = 0.0f;
-	out[0] = (float)m.type;
-	out[1] = (float)m.pointCount;
-	if (m.pointCount == 0) return;
-	out[2] = m.localNormal.x;
-	out[3] = m.localNormal.y;
-	out[4] = m.localPoint.x;
-	out[5] = m.localPoint.y;
-	for (int k = 0; k < m.pointCount; ++k)
-	{
-		float* q = out + 6 + 5 * k;
-		q[0] = m.p[k].x;
-		q[1] = m.p[k].y;
-		memcpy(q + 4, &m.id[k], 4);
-	}
+	caseCollide((const ShapeRec*)shapeA, xfA, (const ShapeRec*)shapeB, xfB, out);
 }
 
 void probe_shape_aabb(const void* shape, const float* xf, float* out4)
 {
-	Xf a;
-	a.p = v2(xf[0], xf[1]);
-	a.q = b2dRot(xf[2]);
-	AABB r = b2dShapeAABB((const ShapeRec*)shape, a);
-	out4[0] = r.lo.x;
-	out4[1] = r.lo.y;
-	out4[2] = r.hi.x;
-	out4[3] = r.hi.y;
+	caseShapeAABB((const ShapeRec*)shape, xf, out4);
 }
 
-// Same layouts as the harness probes b2h_probe_distance / b2h_probe_toi (box2d-mt_amd/harness/harness.cpp).
-static Sweep SweepFrom9(const float* s9)
-{
-	Sweep s;
-	s.localCenter = v2(s9[0], s9[1]);
-	s.c0 = v2(s9[2], s9[3]);
-	s.c = v2(s9[4], s9[5]);
-	s.a0 = s9[6];
-	s.a = s9[7];
-	s.alpha0 = s9[8];
-	return s;
-}
-
+// Same layouts as the harness probes b2h_probe_distance / b2h_probe_toi / b2h_probe_shape_cast (box2d-mt_amd/harness/harness.cpp).
 void probe_distance(int countA, const float* vertsA, float radiusA, const float* xfA, int countB, const float* vertsB,
 	float radiusB, const float* xfB, int useRadii, float* out6)
 {
-	GjkProxy pA = { (const V2*)vertsA, countA, radiusA }, pB = { (const V2*)vertsB, countB, radiusB };
-	Xf a, b;
-	a.p = v2(xfA[0], xfA[1]);
-	a.q = b2dRot(xfA[2]);
-	b.p = v2(xfB[0], xfB[1]);
-	b.q = b2dRot(xfB[2]);
-	GjkCache cache;
-	memset(&cache, 0, sizeof(cache));
-	GjkOutput out;
-	b2dDistance(out, cache, pA, a, pB, b, useRadii != 0);
-	out6[0] = out.pointA.x; out6[1] = out.pointA.y;
-	out6[2] = out.pointB.x; out6[3] = out.pointB.y;
-	out6[4] = out.distance;
-	out6[5] = (float)out.iterations;
+	caseDistance(countA, vertsA, radiusA, xfA, countB, vertsB, radiusB, xfB, useRadii, out6);
+}
+
+void probe_shape_cast(int countA, const float* vertsA, float radiusA, const float* xfA, int countB, const float* vertsB,
+	float radiusB, const float* xfB, float tx, float ty, float* out7)
+{
+	const float travel[2] = { tx, ty };
+	caseShapeCast(countA, vertsA, radiusA, xfA, countB, vertsB, radiusB, xfB, travel, out7);
+}
+
+// ray5 = p1, p2, maxFraction ; out4 = hit, fraction, normal
+void probe_shape_raycast(const void* shape, const float* xf, const float* ray5, float* out4)
+{
+	caseRayCast((const ShapeRec*)shape, xf, ray5, out4);
+}
+
+int probe_test_point(const void* shape, const float* xf, const float* p2)
+{
+	return caseTestPoint((const ShapeRec*)shape, xf, p2);
+}
+
+// out4 = mass, center, inertia about the shape's origin
+void probe_shape_mass(const void* shape, float density, float* out4)
+{
+	caseShapeMass((const ShapeRec*)shape, density, out4);
+}
+
+// b2dPolygonFromPoints + b2dPolygonFinish + b2dShapeMass in b2h_probe_polygon's layout: inp17 = count, 8 points
+void probe_polygon(const float* inp17, float density, float* out39)
+{
+	casePolygon(inp17, density, out39);
 }
 
 // ownIdBlock (b2d_math.h) against the integer remainder: every block count up to `nbMax`, every `stride`-th body id below
@@ -135,12 +115,7 @@ long probe_own_id_block_check(int nbMax, unsigned bodies, unsigned stride)
 void probe_toi(int countA, const float* vertsA, float radiusA, const float* sweepA9, int countB, const float* vertsB,
 	float radiusB, const float* sweepB9, float tMax, float* out2)
 {
-	GjkProxy pA = { (const V2*)vertsA, countA, radiusA }, pB = { (const V2*)vertsB, countB, radiusB };
-	Sweep sA = SweepFrom9(sweepA9), sB = SweepFrom9(sweepB9);
-	float t = 0.0f;
-	int state = b2dTimeOfImpact(&t, pA, sA, pB, sB, tMax);
-	out2[0] = (float)state;
-	out2[1] = t;
+	caseToi(countA, vertsA, radiusA, sweepA9, countB, vertsB, radiusB, sweepB9, tMax, out2);
 }
 
 } // extern "C"

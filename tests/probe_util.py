@@ -7,14 +7,17 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE_SRC = os.path.join(ROOT, "tests", "probe", "host_probe.cpp")
+PROBE_CASES = os.path.join(ROOT, "tests", "probe", "probe_cases.h")
 PROBE_LIB = os.path.join(ROOT, "tests", "probe", "libhost_probe.so")
+DEVICE_PROBE_LIB = os.path.join(ROOT, "tests", "probe", "libdevice_probe.so")
 
 CIRCLE, EDGE, POLYGON = 0, 1, 2
 
 
 def build_probe():
-    hdrs = [os.path.join(ROOT, "box2d-mt_amd", "csrc", h) for h in ("b2d_math.h", "b2d_collide.h", "b2d_solver.h", "b2d_toi.h")]
-    newest = max(os.path.getmtime(p) for p in hdrs + [PROBE_SRC])
+    hdrs = [os.path.join(ROOT, "box2d-mt_amd", "csrc", h) for h in ("b2d_math.h", "b2d_collide.h", "b2d_solver.h", "b2d_toi.h",
+                                                                     "b2d_shape_geom.h", "b2d_shapecast.h")]
+    newest = max(os.path.getmtime(p) for p in hdrs + [PROBE_SRC, PROBE_CASES])
     if not os.path.exists(PROBE_LIB) or os.path.getmtime(PROBE_LIB) < newest:
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
                                "-I", os.path.join(ROOT, "box2d-mt_amd", "csrc"), "-o", PROBE_LIB, PROBE_SRC])
@@ -54,3 +57,19 @@ def edge_rec(edge10):
     e = np.asarray(edge10, np.float32)
     flags = (1 if e[4] != 0 else 0) | (2 if e[7] != 0 else 0)
     return shape_rec(EDGE, flags, 0.01, (0, 0), [e[0], e[1], e[2], e[3], e[5], e[6], e[8], e[9]])
+
+
+def proxy_of(rec):
+    """(count, verts as 16 floats, radius) of a shape record, as b2dProxy (b2d_toi.h) takes them"""
+    iv = rec.view(np.int32)
+    n = 1 if iv[0] == CIRCLE else (2 if iv[0] in (EDGE, 3) else int(iv[1]))
+    return n, np.ascontiguousarray(rec[6:22]), float(rec[2])
+
+
+def cast_fields(want7):
+    """Which of b2h_probe_shape_cast's 7 outputs a recorded cast defines: a miss only its flag; a hit everything - but for a hit
+    without an iteration (the skins touch at the start) the reference's point is uninitialised memory (see
+    tests/golden/make_golden_geom.py), so flag, normal, lambda and iterations."""
+    if want7[0] == 0:
+        return [0]
+    return [0, 3, 4, 5, 6] if want7[6] == 0 else list(range(7))

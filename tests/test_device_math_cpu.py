@@ -94,3 +94,117 @@ def test_own_id_block_is_the_exact_remainder():
     P.probe_own_id_block_check.restype = C.c_long
     assert P.probe_own_id_block_check(C.c_int(1024), C.c_uint(2000000), C.c_uint(257)) == 0
 
+
+
+# ---- one-shape geometry: ray cast, point test, AABB, mass, shape cast, polygon build (geom_vectors.npz, polygon_vectors.npz) ----
+def _geom():
+    return np.load(os.path.join(GOLD, "geom_vectors.npz"))
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def test_geom_vectors_cover_what_they_claim():
+    """The coverage conditions of tests/golden/make_golden_geom.py, on the committed file: hit rates of the random vectors per
+    shape kind within 25 % .. 75 %, at least 20 vectors of every special kind - all from the reference's recorded outputs."""
+    import sys
+    sys.path.insert(0, GOLD)
+    import make_golden_geom as mg
+    v = _geom()
+    assert v["ray_kinds"].tolist() == mg.RAY_KINDS and v["point_kinds"].tolist() == mg.POINT_KINDS
+    assert v["cast_kinds"].tolist() == mg.CAST_KINDS and v["classes"].tolist() == mg.CLASSES
+    mg.check_coverage(v)
+    assert os.path.getsize(os.path.join(GOLD, "geom_vectors.npz")) < 300 * 1024
+
+
+def test_device_shape_raycast_header_matches_golden():
+    """b2d_shape_geom.h b2dShapeRayCast against the reference's b2Shape::RayCast: a hit compares flag, fraction and normal
+    bitwise, a miss the flag."""
+    P = pu.build_probe()
+    v = _geom()
+    shapes = np.ascontiguousarray(v["shapes"])
+    bad = hits = 0
+    for s, xf, ray, want in zip(v["ray_shape"], v["ray_xf"], v["ray_in"], v["ray_out"]):
+        out = np.zeros(4, np.float32)
+        xf, ray = np.ascontiguousarray(xf), np.ascontiguousarray(ray)
+        P.probe_shape_raycast(_vp(shapes[s]), xf.ctypes.data_as(fp), ray.ctypes.data_as(fp), out.ctypes.data_as(fp))
+        n = 4 if want[0] else 1
+        bad += not np.array_equal(out[:n].view(np.uint32), want[:n].view(np.uint32))
+        hits += want[0] > 0
+    assert hits > 500
+    assert bad == 0
+
+
+def test_device_test_point_header_matches_golden():
+    """b2d_shape_geom.h b2dShapeTestPoint against the reference's b2Shape::TestPoint (box vertices and face midpoints included)."""
+    P = pu.build_probe()
+    v = _geom()
+    shapes = np.ascontiguousarray(v["shapes"])
+    bad = 0
+    for s, xf, p, want in zip(v["pt_shape"], v["pt_xf"], v["pt_in"], v["pt_out"]):
+        xf, p = np.ascontiguousarray(xf), np.ascontiguousarray(p)
+        bad += P.probe_test_point(_vp(shapes[s]), xf.ctypes.data_as(fp), p.ctypes.data_as(fp)) != int(want)
+    assert bad == 0
+
+
+def test_device_shape_aabb_header_matches_golden():
+    """b2d_collide.h b2dShapeAABB against the reference's b2Shape::ComputeAABB (a chain child has no radius in its box)."""
+    P = pu.build_probe()
+    v = _geom()
+    shapes = np.ascontiguousarray(v["shapes"])
+    bad = 0
+    for s, xf, want in zip(v["aabb_shape"], v["aabb_xf"], v["aabb_out"]):
+        out = np.zeros(4, np.float32)
+        xf = np.ascontiguousarray(xf)
+        P.probe_shape_aabb(_vp(shapes[s]), xf.ctypes.data_as(fp), out.ctypes.data_as(fp))
+        bad += not np.array_equal(out.view(np.uint32), want.view(np.uint32))
+    assert bad == 0
+
+
+def test_device_shape_mass_header_matches_golden():
+    """b2d_shape_geom.h b2dShapeMass against the reference's ComputeMass: circles and edges here, polygons with their build below."""
+    P = pu.build_probe()
+    v = _geom()
+    shapes = np.ascontiguousarray(v["shapes"])
+    bad = 0
+    for s, density, want in zip(v["mass_shape"], v["mass_density"], v["mass_out"]):
+        out = np.zeros(4, np.float32)
+        P.probe_shape_mass(_vp(shapes[s]), C.c_float(density), out.ctypes.data_as(fp))
+        bad += not np.array_equal(out.view(np.uint32), want.view(np.uint32))
+    assert bad == 0
+
+
+def test_device_shape_cast_header_matches_golden():
+    """b2d_shapecast.h b2dShapeCast against the reference's b2ShapeCast: a hit compares point, normal, lambda and iterations
+    bitwise, a miss (overlapping starts among them) the flag; a hit without an iteration all but the point (pu.cast_fields)."""
+    P = pu.build_probe()
+    v = _geom()
+    bad = hits = 0
+    proxies = [pu.proxy_of(r) for r in v["shapes"]]
+    for sa, sb, xa, xb, t, want in zip(v["cast_shapeA"], v["cast_shapeB"], v["cast_xfA"], v["cast_xfB"], v["cast_t"], v["cast_out"]):
+        (na, va, ra), (nb, vb, rb) = proxies[sa], proxies[sb]
+        out = np.zeros(7, np.float32)
+        xa, xb = np.ascontiguousarray(xa), np.ascontiguousarray(xb)
+        P.probe_shape_cast(na, va.ctypes.data_as(fp), C.c_float(ra), xa.ctypes.data_as(fp), nb, vb.ctypes.data_as(fp), C.c_float(rb),
+                           xb.ctypes.data_as(fp), C.c_float(t[0]), C.c_float(t[1]), out.ctypes.data_as(fp))
+        f = pu.cast_fields(want)
+        bad += not np.array_equal(out[f].view(np.uint32), want[f].view(np.uint32))
+        hits += len(f) == 7
+    assert hits > 300
+    assert bad == 0
+
+
+def test_device_polygon_build_header_matches_golden():
+    """b2d_shape_geom.h b2dPolygonFromPoints / b2dPolygonFinish / b2dShapeMass against the reference's b2PolygonShape::Set and
+    ComputeMass: count, vertices, normals, centroid, mass, centre and inertia bitwise (vector i has the density 1 + 0.01 i)."""
+    P = pu.build_probe()
+    v = np.load(os.path.join(GOLD, "polygon_vectors.npz"))
+    bad = 0
+    for i, (inp, want) in enumerate(zip(v["inp"], v["out"])):
+        out = np.zeros(39, np.float32)
+        inp = np.ascontiguousarray(inp)
+        P.probe_polygon(inp.ctypes.data_as(fp), C.c_float(1.0 + 0.01 * i), out.ctypes.data_as(fp))
+        bad += not np.array_equal(out.view(np.uint32), want.view(np.uint32))
+    assert len(v["inp"]) == 200
+    assert bad == 0
