@@ -458,4 +458,309 @@ __global__ __launch_bounds__(RADIX_THREADS) void k_radix_scatter(const uint64_t*
 	}
 }
 
+// ---- one launch per pass ----------------------------------------------------------------------------------------------------
+// The three launches of a pass (histogram, scan of the tiles x digits matrix, scatter) as ONE: at 260 tiles each of them sits
+// at its latency floor, so a pass costs its launch boundaries, not its data. One launch in front of the sort
+// (k_radix_prepare) reads the keys once and leaves the GLOBAL digit histogram of every pass; a pass kernel then
+//   1. turns its pass's histogram into the global base of every digit (a block scan of <= 2 048 counters),
+//   2. ranks the tile's keys with the ballots k_radix_scatter uses, each wave a quarter of the tile on counters of its own (one
+//      barrier per tile, not four per round) - the ranks stay in registers, the tile's per-digit counts fall out of the ranking,
+//   3. publishes the counts, one tagged word per digit,
+//   4. looks back: per digit, the keys of that digit in the tiles before it,
+//   5. scatters: global base + keys in earlier tiles + rank inside the tile. Same places as the three-launch form, bit for bit.
+// The look-back has two levels so that no tile reads more than 15 + tiles / 16 words per digit and nothing forms a chain:
+//   counts[t][q]   (tag << 16) | keys of digit q in tile t (<= 2 048), published by every tile BEFORE it waits for anything
+//   groups[g][q]   (tag << 16) | keys of digit q in tiles [16 g, 16 g + 16) (<= 32 768), published by the group's last tile as
+//                  soon as it has read the 15 counts before its own
+// Tile t reads counts[16 g .. t) of its own group g = t / 16, then groups[0 .. g). (The running inclusive prefix of the
+// classic decoupled look-back never helps here: up to a thousand tiles of 50 KB LDS are resident at once and start together,
+// so no predecessor is ever a whole look-back ahead - a tile would walk all the way down, 260 words per digit, or wait on a
+// chain of 260 tiles. A count depends on nothing, a group sum on counts only: two memory round trips.)
+// `tag` is unique per pass (RadixStatus::epoch, 16 bits; the host zeroes both arrays on the stream before it wraps), so the
+// words are never reset and value and tag arrive in one store. Progress: a tile waits for words of LOWER tiles only, and
+// workgroups are dispatched in index order (the tile index IS blockIdx.x) - the argument of k_scan_chain. Every wait is bounded
+// the same way: SCAN_SPIN_MAX polls, SCAN_ABORT_BIT in *abortWord, a waiter that gives up takes zero for the word and goes on
+// (it still publishes its group's sum, so nobody waits for it; partial sums only ever point below the true place, and the
+// scatter checks the bound anyway). The host finds the bit in the step's read-back and fails the step.
+#define RADIX_MAX_PASSES 6             // one-launch form: the passes one k_radix_prepare counts for (48 KB of LDS)
+#define RADIX_GROUP 16
+#define RADIX_ONEPASS_MAX_TILES 1024   // 2 M keys: 64 group words per digit at most
+#define RADIX_PREPARE_TILES 2          // tiles per workgroup of k_radix_prepare (fewer flushes into the global histograms)
+
+struct RadixLayout
+{
+	int passes;
+	int shift[RADIX_MAX_PASSES];
+	int width[RADIX_MAX_PASSES];
+};
+
+// The global digit histograms of all passes: hist[p * RADIX_DIGITS + digit], zero when the kernel starts (the prepare launch of
+// the sort before this one zeroed it: `histNext` is the other of two buffers), and k_radix_count's job - the tile clamp and the
+// overflow bit.
+__global__ __launch_bounds__(RADIX_THREADS) void k_radix_prepare(const uint64_t* __restrict__ keys, const int* nPtr, int tilesCap, RadixLayout lay,
+	int* __restrict__ hist, int* __restrict__ histNext, int* overflow, int overflowBit)
+{
+	__shared__ int lh[RADIX_MAX_PASSES][RADIX_DIGITS];
+	for (int q = blockIdx.x * RADIX_THREADS + threadIdx.x; q < RADIX_MAX_PASSES * RADIX_DIGITS; q += gridDim.x * RADIX_THREADS) histNext[q] = 0;
+	int n = *nPtr;
+	if (n <= 0) return;
+	int numTiles = (n + RADIX_TILE - 1) / RADIX_TILE;
+	if (numTiles > tilesCap)
+	{
+		if (overflow != nullptr && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(overflow, overflowBit);
+		numTiles = tilesCap;
+		n = numTiles * RADIX_TILE;
+	}
+	const int base = blockIdx.x * (RADIX_PREPARE_TILES * RADIX_TILE);
+	if (base >= n) return;
+	for (int p = 0; p < lay.passes; ++p)
+		for (int q = threadIdx.x; q < (1 << lay.width[p]); q += RADIX_THREADS) lh[p][q] = 0;
+	__syncthreads();
+	// (neighbouring keys often share a digit - the pair search emits a proxy's pairs in a row, so the high digits of a wave's 64 keys
+	// are a handful of runs - and 64 adds to one LDS word are served one after the other: the first lane of a run adds its length)
+	const int lane = threadIdx.x & 63;
+	for (int k = 0; k < RADIX_PREPARE_TILES * RADIX_ITEMS; ++k)
+	{
+		const int i = base + k * RADIX_THREADS + threadIdx.x;
+		const bool valid = i < n;
+		const uint64_t key = valid ? keys[i] : 0;
+		const int nValid = __popcll(__ballot(valid)); // (the valid lanes of a wave are its first ones)
+		for (int p = 0; p < lay.passes; ++p)
+		{
+			const int d = valid ? (int)((uint32_t)(key >> lay.shift[p]) & ((1u << lay.width[p]) - 1u)) : -1;
+			const int prev = __shfl_up(d, 1);
+			const bool head = valid && (lane == 0 || prev != d);
+			const unsigned long long heads = __ballot(head);
+			if (head)
+			{
+				const unsigned long long rest = lane < 63 ? heads >> (lane + 1) : 0ull;
+				const int end = rest ? lane + __ffsll((long long)rest) : nValid;
+				atomicAdd(&lh[p][d], end - lane);
+			}
+		}
+	}
+	__syncthreads();
+	for (int p = 0; p < lay.passes; ++p)
+		for (int q = threadIdx.x; q < (1 << lay.width[p]); q += RADIX_THREADS)
+		{
+			const int v = lh[p][q];
+			if (v) atomicAdd(&hist[p * RADIX_DIGITS + q], v);
+		}
+}
+
+// One status word of another tile: `word` is what a first load saw; polls until the word carries `tag` (bounded, see above).
+__device__ __forceinline__ int radixAwait(const unsigned* p, unsigned word, unsigned tag, int* abortWord, bool& gaveUp)
+{
+	unsigned polls = 0;
+	while (!gaveUp && (word >> 16) != tag)
+	{
+		word = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if ((++polls & 0xfffu) == 0u)
+		{
+			if (polls >= SCAN_SPIN_MAX) atomicOr(abortWord, SCAN_ABORT_BIT);
+			gaveUp = (__hip_atomic_load(abortWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & SCAN_ABORT_BIT) != 0;
+		}
+	}
+	return (word >> 16) == tag ? (int)(word & 0xffffu) : 0;
+}
+
+__global__ __launch_bounds__(RADIX_THREADS) void k_radix_onepass(const uint64_t* __restrict__ keysIn, const int2* __restrict__ valsIn,
+	uint64_t* __restrict__ keysOut, int2* __restrict__ valsOut, const int* __restrict__ passHist, unsigned* counts, unsigned* groups,
+	const int* nPtr, int shift, int width, unsigned tag, int* abortWord)
+{
+	__shared__ int waveCount[4][RADIX_DIGITS]; // per wave: keys of the digit in its quarter so far; after the ranking: in the quarters before it
+	__shared__ int digitBase[RADIX_DIGITS];    // keys of the digit in the tile
+	__shared__ int digitOff[RADIX_DIGITS];     // where the tile's first key of the digit goes
+	__shared__ int scanLds[2 * SCAN_THREADS];
+	int n = *nPtr;
+	if (n <= 0) return;
+	int numTiles = (n + RADIX_TILE - 1) / RADIX_TILE;
+	if (numTiles > (int)gridDim.x) { numTiles = (int)gridDim.x; n = numTiles * RADIX_TILE; } // (k_radix_prepare has flagged it)
+	const int tile = blockIdx.x;
+	if (tile >= numTiles) return;
+	const int tid = threadIdx.x;
+	const int lane = tid & 63;
+	const int wave = tid >> 6;
+	const int D = 1 << width;
+	const uint32_t mask = (uint32_t)D - 1u;
+	const int base = tile * RADIX_TILE;
+	uint64_t keyR[RADIX_ITEMS];
+	int2 valR[RADIX_ITEMS];
+	int rank[RADIX_ITEMS];
+	// (a wave takes a quarter of the tile, 64 keys in a row per round: the ranking below then needs no barrier between rounds)
+	const int first0 = base + wave * (RADIX_TILE / 4) + lane;
+#pragma unroll
+	for (int k = 0; k < RADIX_ITEMS; ++k)
+	{
+		const int i = first0 + k * 64;
+		keyR[k] = i < n ? keysIn[i] : 0;
+		valR[k] = i < n ? valsIn[i] : make_int2(0, 0);
+	}
+	for (int q = tid; q < D; q += RADIX_THREADS)
+	{
+		waveCount[0][q] = 0; waveCount[1][q] = 0; waveCount[2][q] = 0; waveCount[3][q] = 0;
+	}
+	{
+		// 1. global base of every digit: exclusive scan of the pass's histogram (eight consecutive digits per thread)
+		constexpr int PER = RADIX_DIGITS / RADIX_THREADS;
+		int h[PER];
+		int sum = 0;
+#pragma unroll
+		for (int k = 0; k < PER; ++k)
+		{
+			const int q = tid * PER + k;
+			h[k] = q < D ? passHist[q] : 0;
+			sum += h[k];
+		}
+		int total;
+		int run = blockExclusiveScan(sum, &total, scanLds);
+#pragma unroll
+		for (int k = 0; k < PER; ++k)
+		{
+			const int q = tid * PER + k;
+			if (q < D) digitOff[q] = run;
+			run += h[k];
+		}
+	}
+	__syncthreads();
+	// 2. the ballot ranking of k_radix_scatter, wave by wave: rank[k] = keys of the same digit before this one in the wave's
+	// quarter. The wave's own row of counters runs along from round to round (written by the first lane of a digit's group and
+	// handed to the group by a shuffle: LDS serves a wave's accesses in program order), so nothing waits for another wave.
+	int* const myCount = waveCount[wave];
+#pragma unroll
+	for (int k = 0; k < RADIX_ITEMS; ++k)
+	{
+		const bool valid = first0 + k * 64 < n;
+		const int d = valid ? (int)((uint32_t)(keyR[k] >> shift) & mask) : -1;
+		unsigned long long peers = __ballot(valid);
+		for (int b = 0; b < width; ++b)
+		{
+			const unsigned long long m = __ballot(valid && ((d >> b) & 1));
+			peers &= ((d >> b) & 1) ? m : ~m;
+		}
+		if (!valid) peers = 0;
+		const unsigned long long lower = peers & ((1ull << lane) - 1ull);
+		const bool first = valid && lower == 0;
+		int before = 0;
+		if (first)
+		{
+			before = myCount[d];
+			myCount[d] = before + __popcll(peers);
+		}
+		before = __shfl(before, valid ? __ffsll((long long)peers) - 1 : lane);
+		rank[k] = before + __popcll(lower);
+	}
+	__syncthreads();
+	// per digit: the waves' counts become the keys of the digit in the waves before, their sum the tile's count
+	for (int q = tid; q < D; q += RADIX_THREADS)
+	{
+		const int c0 = waveCount[0][q], c1 = waveCount[1][q], c2 = waveCount[2][q], c3 = waveCount[3][q];
+		waveCount[0][q] = 0; waveCount[1][q] = c0; waveCount[2][q] = c0 + c1; waveCount[3][q] = c0 + c1 + c2;
+		digitBase[q] = c0 + c1 + c2 + c3;
+	}
+	// 3. the tile's counts (thread tid owns the digits tid, tid + 256, ...: neighbouring lanes, neighbouring words)
+	for (int q = tid; q < D; q += RADIX_THREADS)
+		__hip_atomic_store(counts + (size_t)tile * D + q, (tag << 16) | (unsigned)digitBase[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	// 4. look back (a thread owns the digits tid, tid + 256, ...; two of them at a time so that their loads are in flight together)
+	bool gaveUp = false;
+	const int group = tile / RADIX_GROUP;
+	const int inGroup = tile - group * RADIX_GROUP; // tiles of the own group before this one
+	for (int q0 = tid; q0 < D; q0 += 2 * RADIX_THREADS)
+	{
+		const bool two = q0 + RADIX_THREADS < D;
+		const unsigned* srcA = counts + (size_t)(group * RADIX_GROUP) * D + q0;
+		const unsigned* srcB = srcA + RADIX_THREADS;
+		unsigned wordA[RADIX_GROUP - 1], wordB[RADIX_GROUP - 1];
+#pragma unroll
+		for (int j = 0; j < RADIX_GROUP - 1; ++j)
+		{
+			wordA[j] = j < inGroup ? __hip_atomic_load(srcA + (size_t)j * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+			wordB[j] = (two && j < inGroup) ? __hip_atomic_load(srcB + (size_t)j * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+		}
+		int beforeA = 0, beforeB = 0;
+#pragma unroll
+		for (int j = 0; j < RADIX_GROUP - 1; ++j)
+			if (j < inGroup)
+			{
+				beforeA += radixAwait(srcA + (size_t)j * D, wordA[j], tag, abortWord, gaveUp);
+				if (two) beforeB += radixAwait(srcB + (size_t)j * D, wordB[j], tag, abortWord, gaveUp);
+			}
+		if (inGroup == RADIX_GROUP - 1)
+		{
+			unsigned* dstA = groups + (size_t)group * D + q0;
+			__hip_atomic_store(dstA, (tag << 16) | (unsigned)(beforeA + digitBase[q0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (two) __hip_atomic_store(dstA + RADIX_THREADS, (tag << 16) | (unsigned)(beforeB + digitBase[q0 + RADIX_THREADS]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+		digitOff[q0] += beforeA;
+		if (two) digitOff[q0 + RADIX_THREADS] += beforeB;
+	}
+	for (int q0 = tid; q0 < D; q0 += 2 * RADIX_THREADS)
+	{
+		const bool two = q0 + RADIX_THREADS < D;
+		int beforeA = 0, beforeB = 0;
+		for (int g0 = 0; g0 < group; g0 += 16)
+		{
+			const unsigned* srcA = groups + (size_t)g0 * D + q0;
+			const unsigned* srcB = srcA + RADIX_THREADS;
+			const int m = group - g0; // (the first 16 of them in this round)
+			unsigned wordA[16], wordB[16];
+#pragma unroll
+			for (int j = 0; j < 16; ++j)
+			{
+				wordA[j] = j < m ? __hip_atomic_load(srcA + (size_t)j * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+				wordB[j] = (two && j < m) ? __hip_atomic_load(srcB + (size_t)j * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+			}
+#pragma unroll
+			for (int j = 0; j < 16; ++j)
+				if (j < m)
+				{
+					beforeA += radixAwait(srcA + (size_t)j * D, wordA[j], tag, abortWord, gaveUp);
+					if (two) beforeB += radixAwait(srcB + (size_t)j * D, wordB[j], tag, abortWord, gaveUp);
+				}
+		}
+		digitOff[q0] += beforeA;
+		if (two) digitOff[q0 + RADIX_THREADS] += beforeB;
+	}
+	__syncthreads();
+	// 5. scatter
+#pragma unroll
+	for (int k = 0; k < RADIX_ITEMS; ++k)
+	{
+		if (first0 + k * 64 < n)
+		{
+			const int d = (int)((uint32_t)(keyR[k] >> shift) & mask);
+			const int dst = digitOff[d] + myCount[d] + rank[k];
+			if ((unsigned)dst < (unsigned)n) // (always, unless a look-back gave up)
+			{
+				keysOut[dst] = keyR[k];
+				valsOut[dst] = valR[k];
+			}
+		}
+	}
+}
+
+// The status words of the one-launch passes, one set per world. `counts` holds maxTiles * RADIX_DIGITS words, `groups`
+// (maxTiles / RADIX_GROUP + 1) * RADIX_DIGITS, `hist` two buffers of RADIX_MAX_PASSES * RADIX_DIGITS ints; all zeroed when allocated.
+struct RadixStatus
+{
+	unsigned* counts = nullptr;
+	unsigned* groups = nullptr;
+	size_t countsCap = 0, groupsCap = 0; // words
+	int* hist = nullptr;
+	int maxTiles = 0;        // the tiles `counts` / `groups` are sized for (<= RADIX_ONEPASS_MAX_TILES); 0: three-launch passes only
+	unsigned epoch = 0;      // tag of the last pass (16 bits, never 0)
+	unsigned parity = 0;     // which half of `hist` the next sort counts into
+	int* abortWord = nullptr;
+};
+
+// Whether a sort can take the one-launch form.
+static inline bool radixOnepassFits(hipStream_t stream, const RadixStatus& rs, int tilesCap, size_t passes)
+{
+	if (rs.maxTiles <= 0 || tilesCap > rs.maxTiles || passes == 0 || passes > RADIX_MAX_PASSES) return false;
+	// (a captured launch would replay its tags and its histogram parity: the three-launch form, as deviceExclusiveScan)
+	hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+	(void)hipStreamIsCapturing(stream, &capturing);
+	return capturing == hipStreamCaptureStatusNone;
+}
+
 #endif

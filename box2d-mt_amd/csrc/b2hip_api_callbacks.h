@@ -182,6 +182,8 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 
 // Debug hook: raw read of a device array (0 b_pos, 1 b_vel, 2 li_bodies, 3 b_force, 4 b_flags, 5 b_damp, 6 b_mass,
 // 7 counters as ints) into `out` (bytes).
+// 22: pair-update statistics since the world was created, `count` (<= 2) long longs from `first`: [0] radix sorts queued,
+//     [1] of them in the one-launch form (b2d_scan.h: k_radix_prepare + one k_radix_onepass per pass).
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -221,10 +223,79 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 	case 19: src = w->rowColor.p; elem = 4; break;
 	case 20: src = w->blkRowStart.p; elem = 4; break;
 	case 21: src = w->bodyRest.p; elem = 8; break;
+	case 22:
+	{
+		const long long stats[2] = { w->statSorts, w->statSortsOnepass };
+		if (first < 0 || count < 0 || first + count > 2) return setError(B2HIP_ERR_INVALID, "pair-update statistics: [0, 2)");
+		memcpy(out, stats + first, (size_t)count * sizeof(long long));
+		return 0;
+	}
 	default: return setError(B2HIP_ERR_INVALID, "bad array id");
 	}
 	HIP_TRY(hipMemcpy(out, (const char*)src + (size_t)first * elem, (size_t)count * elem, hipMemcpyDeviceToHost));
 	return 0;
+}
+
+// Test hook: radixSort (b2hip_host_phases.h) over the caller's arrays on the world's stream - `count` keys with two payload
+// ints each, sorted in place by the passes (shift, width <= RADIX_BITS) given, in the form the world would take for a sort of
+// count / RADIX_TILE + 1 tiles (B2HIP_SORT_ONEPASS, RADIX_ONEPASS_MAX_TILES, RADIX_MAX_PASSES).
+int b2hip_test_radix_sort(b2hip_world* w, int count, uint64_t* keys, int* payloads, int passes, const int* shifts, const int* widths)
+{
+	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
+	DEVICE_GUARD(w);
+	if (count < 0 || passes < 1 || !shifts || !widths || (count > 0 && (!keys || !payloads))) return setError(B2HIP_ERR_INVALID, "bad argument");
+	if (w->stepActive) return setError(B2HIP_ERR_INVALID, "inside a step");
+	std::vector<std::pair<int, int>> lay;
+	for (int p = 0; p < passes; ++p)
+	{
+		if (widths[p] < 1 || widths[p] > RADIX_BITS || shifts[p] < 0 || shifts[p] + widths[p] > 64) return setError(B2HIP_ERR_INVALID, "bad pass");
+		lay.push_back(std::make_pair(shifts[p], widths[p]));
+	}
+	int rc = ensureCapacity(w, 0);
+	if (rc) return rc;
+	hipStream_t s = w->stream;
+	const int tilesCap = count / RADIX_TILE + 1;
+	// the scratch of either form for that many tiles (ensureCapacity sizes it for the world's pair buffers)
+	const size_t tiles = (size_t)tilesCap + 1;
+	rc = w->radixHist.ensure(RADIX_DIGITS * tiles + 2, s); if (rc) return rc;
+	rc = w->radixHistScan.ensure(RADIX_DIGITS * tiles + 4, s); if (rc) return rc;
+	rc = w->scanTmp.ensure(3 * (RADIX_DIGITS * tiles / SCAN_TILE + 8), s); if (rc) return rc;
+	rc = w->scanFlags.ensure(RADIX_DIGITS * tiles / SCAN_TILE + 8, s); if (rc) return rc;
+	if (w->sortOnepass)
+	{
+		const size_t onepassTiles = std::min<size_t>(tiles, RADIX_ONEPASS_MAX_TILES);
+		rc = w->radixCounts.ensure(onepassTiles * RADIX_DIGITS, s, false); if (rc) return rc;
+		rc = w->radixGroups.ensure((onepassTiles / RADIX_GROUP + 1) * RADIX_DIGITS, s, false); if (rc) return rc;
+	}
+	rc = ensureCapacity(w, 0); // (the kernarg block and the scan / radix contexts point at the grown arrays)
+	if (rc) return rc;
+	DevArray<uint64_t> k0, k1;
+	DevArray<int2> v0, v1;
+	DevArray<int> nDev;
+	const size_t room = (size_t)count + 1;
+	rc = k0.ensure(room, s, false, false);
+	if (!rc) rc = k1.ensure(room, s, false, false);
+	if (!rc) rc = v0.ensure(room, s, false, false);
+	if (!rc) rc = v1.ensure(room, s, false, false);
+	if (!rc) rc = nDev.ensure(1, s, false, true);
+	auto done = [&](int code) { (void)hipStreamSynchronize(s); k0.release(); k1.release(); v0.release(); v1.release(); nDev.release(); return code; };
+	if (rc) return done(rc);
+	hipError_t e = hipMemcpyAsync(nDev.p, &count, sizeof(int), hipMemcpyHostToDevice, s);
+	if (e == hipSuccess && count > 0) e = hipMemcpyAsync(k0.p, keys, (size_t)count * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+	if (e == hipSuccess && count > 0) e = hipMemcpyAsync(v0.p, payloads, (size_t)count * sizeof(int2), hipMemcpyHostToDevice, s);
+	if (e != hipSuccess) return done(setError(B2HIP_ERR_HIP, hipGetErrorString(e)));
+	uint64_t *kin = k0.p, *kout = k1.p;
+	int2 *vin = v0.p, *vout = v1.p;
+	rc = radixSort(w, kin, kout, vin, vout, nDev.p, tilesCap, lay);
+	if (rc) return done(rc);
+	int overflow = 0;
+	e = hipMemcpyAsync(&overflow, &w->d_state.p->c.overflow, sizeof(int), hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess && count > 0) e = hipMemcpyAsync(keys, kin, (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess && count > 0) e = hipMemcpyAsync(payloads, vin, (size_t)count * sizeof(int2), hipMemcpyDeviceToHost, s);
+	if (e == hipSuccess) e = hipStreamSynchronize(s);
+	if (e != hipSuccess) return done(setError(B2HIP_ERR_HIP, hipGetErrorString(e)));
+	if (overflow & SCAN_ABORT_BIT) return done(setError(B2HIP_ERR_HIP, "a look-back of the sort gave up waiting for a predecessor tile"));
+	return done(0);
 }
 
 // Debug hook (B2HIP_TRACE=1): stage labels + state hashes recorded by the last b2hip_solve.

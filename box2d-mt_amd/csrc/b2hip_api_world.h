@@ -231,7 +231,7 @@ void b2hip_world_destroy(b2hip_world* w)
 	w->b_blk1.release(); w->b_adopt.release(); w->b_adoptStage.release(); w->blkRows.release(); w->blkRowStart.release(); w->blkCursor.release(); w->blkBodyCount.release(); w->blkBodyCursor.release();
 	w->blkBodyStart.release(); w->blkBodies.release(); w->rowColor.release(); w->b_cutv.release();
 	w->pairFirst.release(); w->pairRank.release(); w->scanTmp.release(); w->radixHist.release(); w->radixHistScan.release();
-	w->keepFlag.release(); w->keepScan.release(); w->scanTmp4.release(); w->scanFlags.release(); w->stateOut.release(); w->consts.release();
+	w->keepFlag.release(); w->keepScan.release(); w->scanTmp4.release(); w->scanFlags.release(); w->radixCounts.release(); w->radixGroups.release(); w->radixGlobalHist.release(); w->stateOut.release(); w->consts.release();
 	w->qIn.release(); w->qCounts.release(); w->qOffsets.release(); w->qItems.release(); w->qFlags.release(); w->qScanWork.release();
 	w->qScanWords.release(); w->qWords.release(); w->qHits.release(); w->qDistances.release(); w->qPoses.release(); w->qShapes.release();
 	w->qKeys.release(); w->qKeysWork.release(); w->qAny.release();

@@ -34,9 +34,46 @@ static void radixPasses(int first, int bits, std::vector<std::pair<int, int>>& o
 }
 
 // keys / payloads in (kin, vin), *nPtr of them; sorted by the bits the passes name; which buffers hold the result comes back in kin / vin
+// One launch per pass behind one that counts every pass's digits (k_radix_prepare / k_radix_onepass, b2d_scan.h) wherever the
+// status words cover the tiles; three launches per pass (B2HIP_SORT_ONEPASS=0: always) beyond RADIX_ONEPASS_MAX_TILES, for more
+// than RADIX_MAX_PASSES passes and on a stream that is being captured.
 static int radixSort(b2hip_world* w, uint64_t*& kin, uint64_t*& kout, int2*& vin, int2*& vout, const int* nPtr, int tilesCap, const std::vector<std::pair<int, int>>& passes, int overflowBit = 0)
 {
 	DW& d = w->dw;
+	w->statSorts += 1;
+	RadixStatus& rs = w->radixCtx;
+	if (w->sortOnepass && radixOnepassFits(w->stream, rs, tilesCap, passes.size()))
+	{
+		w->statSortsOnepass += 1;
+		if (rs.epoch + passes.size() > 0xffffu)
+		{
+			// (the tag is about to wrap: no word of 65 535 passes ago may read as published - as deviceExclusiveScan's epoch)
+			HIP_TRY(hipMemsetAsync(rs.counts, 0, rs.countsCap * sizeof(unsigned), w->stream));
+			HIP_TRY(hipMemsetAsync(rs.groups, 0, rs.groupsCap * sizeof(unsigned), w->stream));
+			rs.epoch = 0u;
+		}
+		RadixLayout lay;
+		lay.passes = (int)passes.size();
+		for (int p = 0; p < RADIX_MAX_PASSES; ++p)
+		{
+			lay.shift[p] = p < lay.passes ? passes[p].first : 0;
+			lay.width[p] = p < lay.passes ? passes[p].second : 0;
+		}
+		int* hist = rs.hist + rs.parity * (RADIX_MAX_PASSES * RADIX_DIGITS);
+		int* histNext = rs.hist + (1u - rs.parity) * (RADIX_MAX_PASSES * RADIX_DIGITS);
+		rs.parity = 1u - rs.parity;
+		LAUNCH(w, k_radix_prepare, (tilesCap + RADIX_PREPARE_TILES - 1) / RADIX_PREPARE_TILES, RADIX_THREADS, kin, nPtr, tilesCap, lay, hist, histNext,
+			overflowBit ? &d.st->c.overflow : (int*)nullptr, overflowBit);
+		for (size_t p = 0; p < passes.size(); ++p)
+		{
+			const unsigned tag = ++rs.epoch;
+			LAUNCH(w, k_radix_onepass, tilesCap, RADIX_THREADS, kin, vin, kout, vout, (const int*)(hist + p * RADIX_DIGITS), rs.counts, rs.groups, nPtr,
+				passes[p].first, passes[p].second, tag, rs.abortWord);
+			std::swap(kin, kout);
+			std::swap(vin, vout);
+		}
+		return 0;
+	}
 	// (the length of the histogram matrix depends on the count only: once per sort, not once per pass)
 	LAUNCH(w, k_radix_count, 1, 1, nPtr, 0, w->consts.p + 2, tilesCap, overflowBit ? &d.st->c.overflow : (int*)nullptr, overflowBit);
 	for (size_t p = 0; p < passes.size(); ++p)

@@ -249,6 +249,11 @@ struct b2hip_world
 	size_t spUp = 0;                // bodies the device's owner table covers
 	DevArray<int> scanFlags;     // status words of the single-pass scans (b2d_scan.h)
 	ScanFlags scanCtx;           // ... with their epoch and the abort word (refreshed by ensureCapacity)
+	DevArray<unsigned> radixCounts, radixGroups; // status words of the one-launch radix passes (b2d_scan.h)
+	DevArray<int> radixGlobalHist; // ... and the two buffers of the sorts' global digit histograms
+	RadixStatus radixCtx;        // ... with their tag (refreshed by ensureCapacity)
+	bool sortOnepass = true;     // B2HIP_SORT_ONEPASS=0: every radix pass as three launches (histogram, scan, scatter)
+	long long statSorts = 0, statSortsOnepass = 0; // radix sorts queued since the world was created / of them in the one-launch form (b2hip_debug_read 22)
 	DevArray<float> stateOut;
 	DevArray<int> gridBar;       // grid barrier state of the persistent solver
 	int dfEpoch;
@@ -819,6 +824,7 @@ static void readSwitches(b2hip_world* w)
 	w->collideSplitEnv = envInt("B2HIP_COLLIDE_SPLIT", -1);
 	w->collideUniOff = envInt("B2HIP_COLLIDE_UNI", 1) == 0;
 	w->collideSortEnv = envInt("B2HIP_COLLIDE_SORT", -1);
+	w->sortOnepass = envInt("B2HIP_SORT_ONEPASS", 1) != 0;
 	w->collideStage = envInt("B2HIP_COLLIDE_STAGE", -1);
 	w->noSweepBlocks = envSet("B2HIP_NO_SWEEP_BLOCKS");
 	w->tracePartition = envSet("B2HIP_TRACE_PARTITION");
@@ -946,6 +952,15 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 	ENS(scanTmp, 3 * (std::max(maxScanN, RADIX_DIGITS * radixTiles) / SCAN_TILE + 8));
 	ENS(scanTmp4, 3 * (maxScanN / SCAN_TILE + 8));
 	ENS(scanFlags, std::max(maxScanN, RADIX_DIGITS * radixTiles) / SCAN_TILE + 8);
+	// (one-launch radix passes: status words for the pair buffers' tiles up to RADIX_ONEPASS_MAX_TILES - a sort over more takes
+	// the three-launch form; a grown array starts from zeroed words under the running tag, which no word carries yet)
+	const size_t onepassTiles = w->sortOnepass ? std::min<size_t>(radixTiles, RADIX_ONEPASS_MAX_TILES) : 0;
+	if (onepassTiles)
+	{
+		rc = w->radixCounts.ensure(onepassTiles * RADIX_DIGITS, s, false); if (rc) return rc;
+		rc = w->radixGroups.ensure((onepassTiles / RADIX_GROUP + 1) * RADIX_DIGITS, s, false); if (rc) return rc;
+		ENS(radixGlobalHist, 2 * RADIX_MAX_PASSES * RADIX_DIGITS);
+	}
 	ENS(keepFlag, cc + 1); ENS(keepScan, cc + 2);
 	ENS(toiList, cc); ENS(toiPos2c, cc); ENS(toiDestroyList, cc); ENS(toiNewList, TOI_NEW_LIST_MAX);
 	ENS(b_toiGroup, nb); ENS(toiGroups, nb); ENS(toiGroupCount, std::min<size_t>(nb, TOI_GROUPS_MAX)); ENS(toiGroupList, std::min<size_t>(nb, TOI_GROUPS_MAX) * CHAIN_ADJ_MAX); ENS(toiMoved, TOI_MOVED_ALL_MAX); ENS(toiNew, 8 * TOI_NEWPAIR_MAX); ENS(toiParent, nb); ENS(toiDomOf, nb); ENS(toiDomRoot, TOI_DOMAINS_MAX); ENS(toiDomCount, TOI_DOMAINS_MAX); ENS(toiDomBase, TOI_DOMAINS_MAX); ENS(toiDomFill, TOI_DOMAINS_MAX); ENS(toiDomFailed, TOI_DOMAINS_MAX); ENS(toiDomEvents, TOI_DOMAINS_MAX); ENS(toiDomList, cc); ENS(toiHull, np); ENS(snapBody, 5 * nb); ENS(snapFat, np);
@@ -970,6 +985,11 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 	w->scanCtx.words = w->scanFlags.p; // (a grown array keeps its words: the epoch goes on)
 	w->scanCtx.count = w->scanFlags.cap;
 	w->scanCtx.abortWord = &w->d_state.p->c.overflow;
+	w->radixCtx.counts = w->radixCounts.p; w->radixCtx.countsCap = w->radixCounts.cap;
+	w->radixCtx.groups = w->radixGroups.p; w->radixCtx.groupsCap = w->radixGroups.cap;
+	w->radixCtx.hist = w->radixGlobalHist.p;
+	w->radixCtx.maxTiles = w->sortOnepass ? (int)std::min<size_t>(std::min<size_t>(w->radixCounts.cap / RADIX_DIGITS, (w->radixGroups.cap / RADIX_DIGITS) * RADIX_GROUP), RADIX_ONEPASS_MAX_TILES) : 0;
+	w->radixCtx.abortWord = &w->d_state.p->c.overflow;
 	if (w->h_stateCap < 12 * nb + sizeof(DState) / sizeof(float) + 4)
 	{
 		// (the rows of the last read-back are the host's mirror of every body it has not edited: they move along)

@@ -681,6 +681,9 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out);
 int b2hip_debug_trace(b2hip_world* w, int index, char* label, int label_cap, uint64_t* hash);
 /* Raw read-back of one device array (see b2hip.hip for the ids); test / debugging only. */
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out);
+/* Test hook: the world's stable LSD radix sort (the pair update's) over the caller's arrays: `count` keys with two payload
+ * ints each are sorted in place by `passes` passes over the bits [shifts[p], shifts[p] + widths[p]), widths of 1 to 11. */
+int b2hip_test_radix_sort(b2hip_world* w, int count, uint64_t* keys, int* payloads, int passes, const int* shifts, const int* widths);
 
 /* World snapshot (checkpoint / resume; the reference only has the lossy text b2World::Dump, b2World.cpp:2107-2164).
  * Everything that survives a step: bodies, shapes, fixtures with their proxy ids and fat AABBs, joints with their
