@@ -793,6 +793,10 @@ __global__ __launch_bounds__(256) void k_create_contacts(DW W, const uint64_t* k
 	if (createBlocked(W, S, smallPath)) return;
 	const int base = S->c.nContacts;
 	const ContactArrays& C = W.ca[S->cur];
+	// (a kept key set takes the new keys here; a set this update has rebuilt is kept from now on, so it takes them too)
+	const bool ksOn = keysetMaintained(W);
+	const uint32_t ksMask = S->c.ksMask;
+	int ksEmpty = 0;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
 	{
 		if (!W.pairFirst[i]) continue;
@@ -827,6 +831,10 @@ __global__ __launch_bounds__(256) void k_create_contacts(DW W, const uint64_t* k
 		float restitution = mA.y > mB.y ? mA.y : mB.y;
 		C.ids[dst] = make_int4(pA, pB, bodyA, bodyB);
 		C.key[dst] = keys[i];
+		if (ksOn)
+		{
+			ksEmpty += htInsertNew(W, ksMask, keys[i] + 1ull);
+		}
 		C.flags[dst] = flags;
 		C.mat[dst] = make_float4(friction, restitution, 0.0f, 1.0f);
 		C.man0[dst] = make_float4(0, 0, 0, 0);
@@ -842,6 +850,10 @@ __global__ __launch_bounds__(256) void k_create_contacts(DW W, const uint64_t* k
 			W.b_wake[bodyB] = 1;
 		}
 	}
+	// the empty slots consumed go to the fill counter with the arrival of the workgroups, not with one atomic per wave that
+	// created something - thousands of them on one word (the nPairs story of docs/KERNEL_NOTES.md; "tried and not kept" there).
+	// (the condition is the kernel's arguments only: every workgroup arrives, or none)
+	if (W.keysetKeep && !W.spatial) b2dBlockTreeAdd2(W, ARRIVE_KEYSET, &S->c.ksFill, ksEmpty, &S->c.ksFill, 0, (unsigned)W.capPairs <= TREE_SUM_MAX);
 }
 
 __global__ __launch_bounds__(256) void k_create_finish(DW W, int smallPath)
@@ -944,6 +956,7 @@ __global__ __launch_bounds__(1024) void k_toi_order_create(DW W, int smallPath)
 		}
 		else
 		{
+			if (keysetMaintained(W)) S->c.ksStats[KS_INSERTS] += (unsigned long long)S->c.nNewContacts; // (k_create_contacts put their keys into the kept set; a diagnostic: an update in which an insert met its bound - the set is stale then - is not counted)
 			S->c.nContacts = S->c.nContacts + S->c.nNewContacts;
 			S->c.nMoves = 0;
 		}

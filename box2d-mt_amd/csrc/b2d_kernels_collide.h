@@ -843,6 +843,11 @@ __global__ __launch_bounds__(256) void k_flag_filter(DW W, const unsigned long l
 	}
 }
 
+// (the contact-key set's functions, defined below)
+struct DW;
+__device__ __forceinline__ bool keysetMaintained(const DW& W);
+__device__ __forceinline__ bool htDelete(const DW& W, uint32_t mask, uint64_t key);
+
 // Stable compaction (creation order is preserved). keepScan = exclusive scan of keepFlag.
 __global__ __launch_bounds__(256) void k_compact_contacts(DW W)
 {
@@ -852,14 +857,33 @@ __global__ __launch_bounds__(256) void k_compact_contacts(DW W)
 	const int n = S->c.nContacts;
 	const ContactArrays& A = W.ca[S->cur];
 	const ContactArrays& B = W.ca[1 - S->cur];
+	// (a kept key set loses the keys of the contacts dropped here; not while it is stale or invalid - it is rebuilt then)
+	const bool ksOn = keysetMaintained(W);
+	const uint32_t ksMask = S->c.ksMask;
+	int ksTomb = 0, ksLost = 0;
+	__shared__ int s_ks[2];
+	if (threadIdx.x == 0) { s_ks[0] = 0; s_ks[1] = 0; }
+	__syncthreads();
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
 	{
-		if (W.keepFlag[i])
+		// (flags and key are loaded beside the keep flag, not behind it: a dropped contact's probe of the key set starts one
+		// memory round trip earlier, and a kept contact copies both anyway)
+		const int keep = W.keepFlag[i];
+		const uint32_t fl = A.flags[i];
+		const uint64_t key = A.key[i];
+		if (!keep)
+		{
+			if (ksOn && (fl & CF_FOREIGN) == 0)
+			{
+				if (htDelete(W, ksMask, key + 1ull)) ksTomb += 1;
+				else ksLost += 1;
+			}
+		}
+		else
 		{
 			int j = W.keepScan[i];
-			const uint32_t fl = A.flags[i];
 			B.ids[j] = A.ids[i];
-			B.key[j] = A.key[i];
+			B.key[j] = key;
 			B.flags[j] = fl;
 			if ((fl & CF_FOREIGN) == 0)
 			{
@@ -876,17 +900,51 @@ __global__ __launch_bounds__(256) void k_compact_contacts(DW W)
 			if (m >= 0) W.toiPos2c[m] = j;
 		}
 	}
+	// the tombstones written and the keys not found travel with the arrival of the workgroups, as k_collide's census does
+	// (one atomic per wave on the two counters is 8 000 of them queueing on one line: docs/KERNEL_NOTES.md, "tried and not kept")
+	const bool fit = (unsigned)W.capContacts <= TREE_SUM_MAX;
+	if (ksOn)
+	{
+		ksTomb = waveSumInt(ksTomb);
+		ksLost = waveSumInt(ksLost);
+		if (waveLane() == 0)
+		{
+			if (ksTomb) atomicAdd(&s_ks[0], ksTomb);
+			if (ksLost) atomicAdd(&s_ks[1], ksLost);
+		}
+	}
+	__syncthreads();
+	unsigned tomb = (unsigned)s_ks[0], lost = (unsigned)s_ks[1];
+	if (!fit && threadIdx.x == 0)
+	{
+		if (tomb) atomicAdd(&S->c.ksStats[KS_TOMBSTONES], (unsigned long long)tomb);
+		if (lost) { atomicAdd(&S->c.ksStats[KS_NOT_FOUND], (unsigned long long)lost); S->c.ksStale = 1; }
+	}
 	// the workgroup that finishes last switches the buffers (was a kernel of its own): everybody has read the count and
 	// the live half by then
 	// (no fence: the last workgroup reads nothing the others wrote - a fence per workgroup writes the L2 back 256 times)
-	if (b2dLastBlockArrive(W, ARRIVE_COMPACT) && threadIdx.x == 0)
+	if (b2dLastBlockArrive(W, ARRIVE_COMPACT, fit ? tomb : 0u, fit ? lost : 0u, &tomb, &lost) && threadIdx.x == 0)
 	{
+		if (fit && tomb) S->c.ksStats[KS_TOMBSTONES] += (unsigned long long)tomb;
+		if (fit && lost) { S->c.ksStats[KS_NOT_FOUND] += (unsigned long long)lost; S->c.ksStale = 1; } // (a key that must be there is not: rebuild)
 		S->c.nContacts = W.keepScan[n];
 		S->cur = 1 - S->cur;
 	}
 }
 
 // ---- contact key hash set ---------------------------------------------------------------------
+// DW::ht_keys: open addressing, linear probing, three slot states.
+//   0            empty
+//   key + 1      live (+1 so that key 0 cannot read as "empty")
+//   HT_TOMB      a key that was deleted: lookups walk past it, an insert may take it
+// No key + 1 equals HT_TOMB: a key is (lower proxy key << 32) | higher proxy key, proxy keys are non-negative ints, so
+// key <= 0x7fffffff7fffffff and key + 1 <= 0x7fffffff80000000.
+// The set survives the step (B2HIP_KEYSET_KEEP, default): k_create_contacts inserts what it creates, k_compact_contacts
+// - which every destroying path goes through - writes a tombstone over what it drops, and a pair update rebuilds the table
+// (k_bp_clear / k_bp_build: exactly the live non-foreign keys) only when keysetDecision says so. Whoever else changes the
+// contact array sets Counters::ksStale (docs/KERNEL_NOTES.md lists the writers).
+#define HT_TOMB 0xffffffffffffffffull
+
 __device__ __forceinline__ uint32_t hashKey(uint64_t k)
 {
 	k ^= k >> 33;
@@ -897,20 +955,59 @@ __device__ __forceinline__ uint32_t hashKey(uint64_t k)
 	return (uint32_t)k;
 }
 
-// The part of the table a pair update uses: sized for the LIVE contacts (at most 25 % load), not for the array's capacity -
-// the table is cleared every update, and the capacity of a world that once saw a burst of pairs (the 1 M-body field:
-// 16 M slots, 128 MB) cost 120 us of clearing per step for 130 000 keys. Every kernel of one update (clear, build, the
-// pair search) derives the same mask from Counters::nContacts, which only the update's own commit changes.
-__device__ __forceinline__ uint32_t htLiveMask(const DW& W)
+// The part of the table a rebuild uses: sized for the LIVE contacts (at most 25 % load), not for the array's capacity -
+// a rebuild clears it, and the capacity of a world that once saw a burst of pairs (the 1 M-body field: 16 M slots, 128 MB)
+// cost 120 us of clearing per step for 130 000 keys. Only the decision and the rebuild ask for it: Counters::nContacts
+// moves between updates while a kept table does not, so everybody else uses Counters::ksMask, the mask of the last rebuild.
+__device__ __forceinline__ uint32_t htWantMask(const DW& W)
 {
 	const uint32_t want = 4u * (uint32_t)W.st->c.nContacts + 1024u;
 	uint32_t m = 0xffffffffu >> __clz((int)(want | 1u)); // next power of two above `want`, minus one
 	return m < W.htMask ? m : W.htMask;
 }
 
-__device__ __forceinline__ void htInsert(const DW& W, uint64_t key)
+// Keep the set (0) or rebuild it (the cause, KS_CAUSE_*)? One answer per pair update, the same in every workgroup of
+// k_bp_clear and k_bp_build: a pure function of kernel arguments and of words nobody writes while the two run - the last
+// workgroup of k_bp_build to arrive commits the new mask, fill and flags (keysetCommit) when all have read the old ones.
+__device__ __forceinline__ int keysetDecision(const DW& W)
 {
-	const uint32_t mask = htLiveMask(W);
+	const Counters& c = W.st->c;
+	if (!W.keysetKeep) return KS_CAUSE_OFF;
+	// (CF_FOREIGN of a contact changes with the ownership of its bodies: a sharded world builds its set every update)
+	if (W.spatial) return KS_CAUSE_SHARDED;
+	if (!c.ksValid) return KS_CAUSE_INVALID;
+	if (c.ksStale) return KS_CAUSE_STALE;
+	const uint32_t want = htWantMask(W), have = c.ksMask;
+	// (a smaller table would do: only beyond a factor of 4, so that a count hovering at a power of two does not rebuild every step)
+	if (want > have || have > W.htMask || ((have + 1u) >> 2) > want + 1u) return KS_CAUSE_MASK;
+	if ((unsigned long long)(unsigned)c.ksFill * 100ull > (unsigned long long)(unsigned)W.keysetMaxFill * ((unsigned long long)have + 1ull)) return KS_CAUSE_FILL;
+	return 0;
+}
+
+// One thread, when every workgroup of k_bp_build has finished.
+__device__ __forceinline__ void keysetCommit(const DW& W, int cause)
+{
+	Counters& c = W.st->c;
+	if (cause)
+	{
+		c.ksMask = htWantMask(W);
+		c.ksFill = c.nContacts; // (kept sets have no foreign contacts; a sharded world's set is never valid)
+		c.ksValid = cause != KS_CAUSE_OFF && cause != KS_CAUSE_SHARDED ? 1 : 0;
+		c.ksStale = 0;
+	}
+	c.ksStats[cause] += 1ull;
+}
+
+// Do k_create_contacts and k_compact_contacts maintain the set? (not when the next update rebuilds it anyway)
+__device__ __forceinline__ bool keysetMaintained(const DW& W)
+{
+	const Counters& c = W.st->c;
+	return W.keysetKeep && !W.spatial && c.ksValid && !c.ksStale;
+}
+
+// The rebuild's insert (an empty table under `mask`, at most half full when all are in)
+__device__ __forceinline__ void htInsert(const DW& W, uint32_t mask, uint64_t key)
+{
 	uint32_t h = hashKey(key) & mask;
 	for (;;)
 	{
@@ -920,40 +1017,59 @@ __device__ __forceinline__ void htInsert(const DW& W, uint64_t key)
 	}
 }
 
+// Insert into a kept set a key that is known to be absent (the search has just answered "not contained", pairFirst has
+// removed the duplicates of this update): the first slot on the probe path that is empty or a tombstone, taken with a CAS
+// against the value seen - another new key may take it first, then the walk goes on. Nobody deletes meanwhile.
+// Returns 1 if an empty slot was consumed (the caller adds these up for Counters::ksFill). The walk is bounded by the
+// table's size: a table without a free slot marks the set stale and leaves the key out - the next update rebuilds.
+__device__ __forceinline__ int htInsertNew(const DW& W, uint32_t mask, uint64_t key)
+{
+	uint32_t h = hashKey(key) & mask;
+	for (uint32_t probes = 0; probes <= mask; ++probes)
+	{
+		const unsigned long long v = W.ht_keys[h];
+		if (v == 0ull || v == HT_TOMB)
+		{
+			if (atomicCAS((unsigned long long*)&W.ht_keys[h], v, (unsigned long long)key) == v) return v == 0ull ? 1 : 0;
+		}
+		h = (h + 1) & mask;
+	}
+	W.st->c.ksStale = 1;
+	return 0;
+}
+
+// Lookup: past tombstones, until the key or an empty slot. The walk is bounded by the table's size (mask + 1 probes): a
+// lookup that reaches the bound has looked at EVERY slot and not seen the key, so "not contained" is exact, not a guess -
+// it is answered, and the set is marked stale so that the next update rebuilds a table that has no empty slot left on
+// this path (the fill limit keeps a valid table far from that; the bound is there so that nothing can spin).
 __device__ __forceinline__ bool htContains(const DW& W, uint64_t key)
 {
-	const uint32_t mask = htLiveMask(W);
+	const uint32_t mask = W.st->c.ksMask;
 	uint32_t h = hashKey(key) & mask;
-	for (;;)
+	for (uint32_t probes = 0; probes <= mask; ++probes)
 	{
-		uint64_t v = W.ht_keys[h];
+		const uint64_t v = W.ht_keys[h];
 		if (v == key) return true;
 		if (v == 0) return false;
 		h = (h + 1) & mask;
 	}
+	W.st->c.ksStale = 1;
+	return false;
 }
 
-__global__ __launch_bounds__(256) void k_ht_clear(DW W)
+// Delete: the slot of a key that must be there becomes a tombstone (a plain store: nobody else writes that slot now).
+// False if the key is not in the table.
+__device__ __forceinline__ bool htDelete(const DW& W, uint32_t mask, uint64_t key)
 {
-	b2dPhaseStamp(W);
-	if (W.st->c.nMoves == 0) return;
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, live = htLiveMask(W); i <= live; i += gridDim.x * blockDim.x)
+	uint32_t h = hashKey(key) & mask;
+	for (uint32_t probes = 0; probes <= mask; ++probes)
 	{
-		W.ht_keys[i] = 0;
+		const uint64_t v = W.ht_keys[h];
+		if (v == key) { W.ht_keys[h] = HT_TOMB; return true; }
+		if (v == 0) return false;
+		h = (h + 1) & mask;
 	}
-}
-
-__global__ __launch_bounds__(256) void k_ht_build(DW W)
-{
-	b2dPhaseStamp(W);
-	DState* S = W.st;
-	if (S->c.nMoves == 0) return;
-	const int n = S->c.nContacts;
-	const ContactArrays& C = W.ca[S->cur];
-	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-	{
-		htInsert(W, C.key[i] + 1ull); // +1 so that key 0 (proxies 0,0 never pair) cannot collide with "empty"
-	}
+	return false;
 }
 
 #endif

@@ -833,6 +833,7 @@ __global__ __launch_bounds__(1024) void k_sp_merge_tails(DW W, const int* in, si
 	{
 		int cands = 0;
 		for (int j = 0; j < total; ++j) cands += s_cand[j];
+		if (total) S->c.ksStale = 1; // (the key set: a sharded world rebuilds it every update anyway)
 		S->c.nContacts = base + total;
 		S->c.nToiOrder = toiOrderBase + cands;
 	}

@@ -1383,6 +1383,7 @@ __device__ __forceinline__ void toiLoopRun(const DW& W, const StepParams& sp, in
 		}
 		else
 		{
+			if (S->c.nContacts != s_nC) S->c.ksStale = 1; // (the key set: contacts created without k_create_contacts)
 			S->c.nContacts = s_nC;
 			if (!partial) S->c.nToiList = s_nL;
 			S->c.nToiEvents = (partial ? S->c.nToiEvents : 0) + s_events;

@@ -193,6 +193,7 @@ __global__ __launch_bounds__(256) void k_toi_snapshot(DW W, int restore)
 			S->c.toiIncomplete = 0;
 			S->c.spToiStraddle = 0;
 			// (the serial replay of tied components may have created contacts)
+			if (S->c.nContacts != S->c.nContactsSnap) S->c.ksStale = 1; // (the key set: contacts leave without k_compact_contacts)
 			S->c.nContacts = S->c.nContactsSnap;
 			S->c.nToiOrder = S->c.nToiOrderSnap;
 		}
@@ -834,6 +835,7 @@ __device__ __forceinline__ void toiChainsEnd(const DW& W)
 			__syncthreads();
 			if (threadIdx.x == 0)
 			{
+				if (s_created) S->c.ksStale = 1; // (the key set: contacts created without k_create_contacts)
 				S->c.nContacts = base + s_created;
 				S->c.nToiChainCreated = s_created;
 			}
@@ -872,8 +874,9 @@ __global__ __launch_bounds__(CHAIN_LANES) void k_toi_chains(DW W, StepParams sp,
 }
 
 // ---- fused front of the pair update: (hash table of contact keys + spatial grid) cleared, then built -----------------
-// Same bodies as k_ht_clear + k_grid_clear(force 0) and k_ht_build + k_grid_count(force 0): independent arrays, one
-// launch each instead of two.
+// The contact-key set and the grid are independent arrays: one launch each for clearing and building both. The set's loops
+// run only when this update rebuilds it (keysetDecision, b2d_kernels_collide.h); the grid, the extent maximum and the
+// counter resets are every update's.
 __global__ __launch_bounds__(256) void k_bp_clear(DW W)
 {
 	b2dPhaseStamp(W);
@@ -915,8 +918,11 @@ __global__ __launch_bounds__(256) void k_bp_clear(DW W)
 			gc[i] = z;
 			gu[i] = z;
 		}
-		int4* hk = (int4*)W.ht_keys;
-		for (uint32_t i = t0, n2 = (htLiveMask(W) + 1u) >> 1; i < n2; i += stride) hk[i] = z; // (the part this update uses)
+		if (keysetDecision(W) != 0)
+		{
+			int4* hk = (int4*)W.ht_keys;
+			for (uint32_t i = t0, n2 = (htWantMask(W) + 1u) >> 1; i < n2; i += stride) hk[i] = z; // (the part the rebuilt set uses)
+		}
 	}
 }
 
@@ -928,8 +934,13 @@ __global__ __launch_bounds__(256) void k_bp_build(DW W)
 	const int stride = gridDim.x * blockDim.x, t0 = blockIdx.x * blockDim.x + threadIdx.x;
 	const int nC = S->c.nContacts;
 	const ContactArrays& C = W.ca[S->cur];
-	// (the pair search asks the set only about pairs of this rank's bodies: another rank's contacts stay out - tryEmitPair)
-	for (int i = t0; i < nC; i += stride) if ((C.flags[i] & CF_FOREIGN) == 0) htInsert(W, C.key[i] + 1ull);
+	const int ksCause = keysetDecision(W);
+	if (ksCause != 0)
+	{
+		// (the pair search asks the set only about pairs of this rank's bodies: another rank's contacts stay out - tryEmitPair)
+		const uint32_t mask = htWantMask(W);
+		for (int i = t0; i < nC; i += stride) if ((C.flags[i] & CF_FOREIGN) == 0) htInsert(W, mask, C.key[i] + 1ull);
+	}
 	const int n = W.nProxies;
 	for (int p = t0; p < n; p += stride)
 	{
@@ -947,6 +958,10 @@ __global__ __launch_bounds__(256) void k_bp_build(DW W)
 			atomicAdd(&W.gridCount[cellHash(ix, iy, W.gridMask)], 1);
 		}
 	}
+	// the workgroup that finishes last commits the decision: every workgroup of this launch (and of k_bp_clear before it) has
+	// read the words it came from by then, and the search kernels behind this one read the committed mask
+	// (no fence: the last workgroup reads nothing the others wrote)
+	if (b2dLastBlockArrive(W, ARRIVE_KEYSET) && threadIdx.x == 0) keysetCommit(W, ksCause);
 }
 
 #endif

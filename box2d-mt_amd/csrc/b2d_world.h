@@ -100,6 +100,20 @@ struct ContactArrays
 	int* mgr;         // TOI candidates: slot in the reference's contact array (b2Contact::m_managerIndex), else -1
 };
 
+// Counters::ksStats
+#define KS_KEPT 0         // pair updates that kept the set
+// [1 .. 6]: rebuilds by cause, numbered as keysetDecision returns them
+#define KS_CAUSE_INVALID 1
+#define KS_CAUSE_STALE 2
+#define KS_CAUSE_MASK 3
+#define KS_CAUSE_FILL 4
+#define KS_CAUSE_SHARDED 5
+#define KS_CAUSE_OFF 6
+#define KS_TOMBSTONES 7   // tombstones written (k_compact_contacts)
+#define KS_INSERTS 8      // keys inserted into a kept set (k_create_contacts; counted at the update's commit)
+#define KS_NOT_FOUND 9    // deletes that found no key
+#define KS_STATS 10
+
 struct Counters
 {
 	int nContacts;       // live contacts
@@ -203,6 +217,14 @@ struct Counters
 	int spToiCreated;    // contacts this rank's TOI phase created (the tail of its contact array until the ranks have merged their tails)
 	int spToiStraddle;   // ... of them with a body of another rank (an event reached over an ownership boundary: refused)
 	int spOwnRows;       // rows k_end_step packed into DW::spOwnOut this step (the bodies this rank owns)
+	// the contact-key set kept across pair updates (b2d_kernels_collide.h: "contact key hash set"); all persistent. The pair
+	// update's decision "keep or rebuild" (keysetDecision) is a function of these four words, nContacts and nMoves: nothing
+	// writes any of them while k_bp_clear / k_bp_build run, except the last workgroup of k_bp_build, when all have read them.
+	int ksValid;         // DW::ht_keys holds exactly the keys of the live non-foreign contacts, under ksMask (0: a new world, a snapshot just loaded, a sharded world, B2HIP_KEYSET_KEEP=0)
+	int ksStale;         // somebody changed the contact array without maintaining the set (or a probe met its bound): the next pair update rebuilds it
+	uint32_t ksMask;     // the mask the table was built with: what every ht* function uses until the next rebuild
+	int ksFill;          // slots that are not empty: live keys + tombstones
+	unsigned long long ksStats[KS_STATS]; // since the world was created (b2hip_debug_read 23), see the KS_* indices
 };
 
 // What b2ContactListener::PreSolve is told about one contact (gathered after Collide, before the compaction of destroyed
@@ -282,6 +304,8 @@ struct DW
 	int smallMaxW;        // islands up to this size take the exact-order in-LDS solver (default TINY_ISLAND_MAX_W = 128; B2HIP_SMALL_MAX_W up to 512)
 	int bigChunks;        // 1: always use 1024-lane chunks for the small-island solver (B2HIP_BIG_CHUNKS)
 	uint32_t htMask;      // contact-key hash table size - 1
+	int keysetKeep;       // B2HIP_KEYSET_KEEP (default 1): the contact-key set survives the step; 0: cleared and built by every pair update
+	int keysetMaxFill;    // B2HIP_KEYSET_MAX_FILL: a kept set is rebuilt when live keys + tombstones exceed this percentage of its slots
 	uint32_t gridMask;    // broad-phase hash grid size - 1
 	float cellSize, invCellSize;
 
@@ -551,7 +575,8 @@ __device__ __forceinline__ float4 b2dLoadAgent4(const float4* p)
 #define ARRIVE_TOI_FIRST 6
 #define ARRIVE_COLOR_CHECK 7
 #define ARRIVE_PAIRS 8
-#define ARRIVE_SITES 9
+#define ARRIVE_KEYSET 9
+#define ARRIVE_SITES 10
 // ONE thread per workgroup, every workgroup of the (one-dimensional) grid exactly once. True in the workgroup that arrives
 // last, with the sums of all workgroups' v0 / v1.
 __device__ __forceinline__ bool b2dTreeArrive(unsigned long long* tree, unsigned v0, unsigned v1, unsigned* t0, unsigned* t1)

@@ -184,6 +184,10 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 // 7 counters as ints) into `out` (bytes).
 // 22: pair-update statistics since the world was created, `count` (<= 2) long longs from `first`: [0] radix sorts queued,
 //     [1] of them in the one-launch form (b2d_scan.h: k_radix_prepare + one k_radix_onepass per pass).
+// 23: the kept contact-key set since the world was created, `count` (<= 12) long longs from `first`: [0] pair updates that
+//     kept the set, [1 .. 6] rebuilds because the set was invalid / stale / built under another mask / too full / the world
+//     is sharded / B2HIP_KEYSET_KEEP=0, [7] tombstones written, [8] keys inserted into a kept set, [9] deletes that found no
+//     key, [10] slots in use now (live + tombstones), [11] the mask now.
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -227,6 +231,18 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 	{
 		const long long stats[2] = { w->statSorts, w->statSortsOnepass };
 		if (first < 0 || count < 0 || first + count > 2) return setError(B2HIP_ERR_INVALID, "pair-update statistics: [0, 2)");
+		memcpy(out, stats + first, (size_t)count * sizeof(long long));
+		return 0;
+	}
+	case 23:
+	{
+		if (first < 0 || count < 0 || first + count > KS_STATS + 2) return setError(B2HIP_ERR_INVALID, "key-set statistics: [0, 12)");
+		Counters c;
+		HIP_TRY(hipMemcpy(&c, &w->d_state.p->c, sizeof(Counters), hipMemcpyDeviceToHost));
+		long long stats[KS_STATS + 2];
+		for (int k = 0; k < KS_STATS; ++k) stats[k] = (long long)c.ksStats[k];
+		stats[KS_STATS] = c.ksFill;
+		stats[KS_STATS + 1] = c.ksMask;
 		memcpy(out, stats + first, (size_t)count * sizeof(long long));
 		return 0;
 	}
@@ -296,6 +312,84 @@ int b2hip_test_radix_sort(b2hip_world* w, int count, uint64_t* keys, int* payloa
 	if (e != hipSuccess) return done(setError(B2HIP_ERR_HIP, hipGetErrorString(e)));
 	if (overflow & SCAN_ABORT_BIT) return done(setError(B2HIP_ERR_HIP, "a look-back of the sort gave up waiting for a predecessor tile"));
 	return done(0);
+}
+
+// Test hook: is the kept contact-key set what it claims to be? Reads only. Two passes behind a synchronisation: over the live
+// contacts (keys of non-foreign contacts the set does not hold) and over the table under its mask (live entries,
+// tombstones). out[0] the set is valid and not stale, [1] missing keys, [2] live entries - non-foreign live contacts (with
+// nothing missing and unique keys, 0 means that no dead contact's entry survives), [3] recounted fill (live + tombstones) -
+// Counters::ksFill, [4] live entries, [5] tombstones.
+__global__ __launch_bounds__(256) void k_keyset_check(DW W, unsigned long long* out)
+{
+	const DState* S = W.st;
+	const ContactArrays& C = W.ca[S->cur];
+	const uint32_t mask = S->c.ksMask;
+	const int stride = (int)(gridDim.x * blockDim.x), t0 = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	int missing = 0, own = 0, live = 0, tomb = 0;
+	for (int i = t0; i < S->c.nContacts; i += stride)
+	{
+		if (C.flags[i] & CF_FOREIGN) continue;
+		own += 1;
+		// (as htContains, without its stale mark)
+		const uint64_t key = C.key[i] + 1ull;
+		uint32_t h = hashKey(key) & mask;
+		bool found = false;
+		for (uint32_t probes = 0; probes <= mask; ++probes)
+		{
+			const uint64_t v = W.ht_keys[h];
+			if (v == key) { found = true; break; }
+			if (v == 0) break;
+			h = (h + 1) & mask;
+		}
+		if (!found) missing += 1;
+	}
+	for (uint32_t i = (uint32_t)t0; i <= mask; i += (uint32_t)stride)
+	{
+		const uint64_t v = W.ht_keys[i];
+		if (v == HT_TOMB) tomb += 1;
+		else if (v != 0) live += 1;
+	}
+	missing = waveSumInt(missing); own = waveSumInt(own); live = waveSumInt(live); tomb = waveSumInt(tomb);
+	if (waveLane() == 0)
+	{
+		if (missing) atomicAdd(&out[0], (unsigned long long)missing);
+		if (own) atomicAdd(&out[1], (unsigned long long)own);
+		if (live) atomicAdd(&out[2], (unsigned long long)live);
+		if (tomb) atomicAdd(&out[3], (unsigned long long)tomb);
+	}
+}
+
+int b2hip_test_keyset_check(b2hip_world* w, long long out[6])
+{
+	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
+	DEVICE_GUARD(w);
+	if (!out) return setError(B2HIP_ERR_INVALID, "null argument");
+	if (w->stepActive) return setError(B2HIP_ERR_INVALID, "inside a step");
+	HIP_TRY(hipStreamSynchronize(w->stream));
+	memset(out, 0, 6 * sizeof(long long));
+	if (!w->d_state.p || !w->ht_keys.p) return 0; // (nothing uploaded yet: no set)
+	Counters c;
+	HIP_TRY(hipMemcpy(&c, &w->d_state.p->c, sizeof(Counters), hipMemcpyDeviceToHost));
+	const bool valid = w->dw.keysetKeep && !w->dw.spatial && c.ksValid && !c.ksStale;
+	out[0] = valid ? 1 : 0;
+	if (c.ksMask > w->dw.htMask) return valid ? setError(B2HIP_ERR_INVALID, "key set: mask beyond the table") : 0;
+	DevArray<unsigned long long> sums;
+	int rc = sums.ensure(4, w->stream, false, true);
+	if (rc) return rc;
+	unsigned long long h[4] = { 0, 0, 0, 0 };
+	hipLaunchKernelGGL(k_keyset_check, dim3(gridFor((size_t)c.ksMask + 1)), dim3(256), 0, w->stream, w->dw, sums.p);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipMemcpyAsync(h, sums.p, sizeof(h), hipMemcpyDeviceToHost, w->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
+	else (void)hipStreamSynchronize(w->stream);
+	sums.release();
+	if (e != hipSuccess) return setError(B2HIP_ERR_HIP, hipGetErrorString(e));
+	out[1] = (long long)h[0];
+	out[2] = (long long)h[2] - (long long)h[1];
+	out[3] = (long long)h[2] + (long long)h[3] - (long long)c.ksFill;
+	out[4] = (long long)h[2];
+	out[5] = (long long)h[3];
+	return 0;
 }
 
 // Debug hook (B2HIP_TRACE=1): stage labels + state hashes recorded by the last b2hip_solve.

@@ -15,7 +15,7 @@ struct SnapHeader
 	float inv_dt0, cellSize;
 	int32_t eventsOn, solverHints; // solverHints: bit 0 serialOrphansNext, bit 1 blocksTooBig, bit 2 step incomplete (sub-stepping), bits 3..7 + 31 freshColors, bits 8..15 adoptSticky, 16..23 largeHintSteps, 24..30 recolorCountdown (what the next island build is told)
 };
-const uint32_t kSnapVersion = 5;
+const uint32_t kSnapVersion = 6;
 const char kSnapMagic[8] = { 'B', '2', 'H', 'I', 'P', 'S', 'N', '1' };
 
 struct SnapWriter
@@ -194,6 +194,10 @@ int b2hip_load_snapshot(const void* buffer, size_t size, int device, b2hip_world
 	DState ds;
 	memcpy(&ds, dsAt, sizeof(ds));
 	if (ds.cur != (int)h.cur || ds.c.nContacts != (int)nC || ds.c.nToiOrder != (int)nT || ds.c.nMoves < (int)nM) return corrupt("device state block");
+	// (the contact-key set is not part of a snapshot: the loaded world's first pair update builds it, and its statistics
+	// start with the new world)
+	ds.c.ksValid = 0; ds.c.ksStale = 0; ds.c.ksMask = 0u; ds.c.ksFill = 0;
+	memset(ds.c.ksStats, 0, sizeof(ds.c.ksStats));
 
 	// ---- device sections: located and range-checked in the blob, uploaded later ---------------------------------------------
 	struct Sec { const void* p; size_t bytes; };

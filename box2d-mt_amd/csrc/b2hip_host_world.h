@@ -825,6 +825,8 @@ static void readSwitches(b2hip_world* w)
 	w->collideUniOff = envInt("B2HIP_COLLIDE_UNI", 1) == 0;
 	w->collideSortEnv = envInt("B2HIP_COLLIDE_SORT", -1);
 	w->sortOnepass = envInt("B2HIP_SORT_ONEPASS", 1) != 0;
+	d.keysetKeep = envInt("B2HIP_KEYSET_KEEP", 1) != 0 ? 1 : 0;
+	d.keysetMaxFill = std::min(std::max(envInt("B2HIP_KEYSET_MAX_FILL", 37), 1), 90); // (per cent; below 100 so that a probe always meets an empty slot)
 	w->collideStage = envInt("B2HIP_COLLIDE_STAGE", -1);
 	w->noSweepBlocks = envSet("B2HIP_NO_SWEEP_BLOCKS");
 	w->tracePartition = envSet("B2HIP_TRACE_PARTITION");
@@ -918,8 +920,12 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 		size_t want = (size_t)nextPow2(2 * cc);
 		if (w->ht_keys.cap < want)
 		{
+			const bool had = w->ht_keys.cap != 0;
 			rc = w->ht_keys.ensure(want, s, false);
 			if (rc) return rc;
+			// (the new table does not keep the old one's keys: a kept set is rebuilt by the next pair update)
+			static const int one = 1;
+			if (had) HIP_TRY(hipMemcpyAsync(&w->d_state.p->c.ksStale, &one, sizeof(int), hipMemcpyHostToDevice, s));
 		}
 	}
 	ENS(parent, nb); ENS(rootSeed, nb); ENS(rootBodies, nb); ENS(rootContacts, nb); ENS(rootJoints, nb); ENS(rootIsland, nb);

@@ -684,6 +684,11 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 /* Test hook: the world's stable LSD radix sort (the pair update's) over the caller's arrays: `count` keys with two payload
  * ints each are sorted in place by `passes` passes over the bits [shifts[p], shifts[p] + widths[p]), widths of 1 to 11. */
 int b2hip_test_radix_sort(b2hip_world* w, int count, uint64_t* keys, int* payloads, int passes, const int* shifts, const int* widths);
+/* Test hook: checks the contact-key set the pair update keeps across steps (B2HIP_KEYSET_KEEP) against the contact array.
+ * Synchronises, reads only. out[0] 1 if the set is kept now (valid and not stale), [1] keys of live contacts the set does
+ * not hold, [2] live entries minus live contacts (entries of dead contacts that survived), [3] recounted minus tracked
+ * fill, [4] live entries, [5] tombstones. A kept set is right when [1] = [2] = [3] = 0. */
+int b2hip_test_keyset_check(b2hip_world* w, long long out[6]);
 
 /* World snapshot (checkpoint / resume; the reference only has the lossy text b2World::Dump, b2World.cpp:2107-2164).
  * Everything that survives a step: bodies, shapes, fixtures with their proxy ids and fat AABBs, joints with their
