@@ -13,6 +13,11 @@
 // queries sort each query's items by fixture id (k_query_sort, k_query_compact_big); rays and shape casts keep the smallest
 // (fraction bits, fixture) key, a total order; the closest distance keeps the smallest (distance bits, fixture) key; the
 // all-hit rays sort each ray's (fraction bits, fixture) keys (k_query_sort_keys, k_query_sort_keys_big).
+//
+// What has one definition here, because its copies would have to agree to the bit: the ray walk's arithmetic (QueryRay: set-up,
+// candidate cull, pieces - shared by the closest, all-hit and any-hit kernels; queryPieceCount / queryPieceSpan also by the
+// shape cast), the keys (queryKey / queryKeyValue / queryKeyFixture), the owner of a flat item (queryOwner), the GJK call of
+// every overlap and distance (queryDistance), and the miss records (queryRayMiss / queryDistanceMiss, host and device).
 #ifndef B2D_KERNELS_QUERY_H
 #define B2D_KERNELS_QUERY_H
 
@@ -35,6 +40,49 @@ __device__ __forceinline__ bool queryFilterPasses(const DW& W, int q, uint32_t m
 __device__ __forceinline__ bool queryBoxSane(float4 b)
 {
 	return fabsf(b.x) <= QUERY_COORD_MAX && fabsf(b.y) <= QUERY_COORD_MAX && fabsf(b.z) <= QUERY_COORD_MAX && fabsf(b.w) <= QUERY_COORD_MAX;
+}
+
+// The (value bits, fixture id) key the closest and the all-hit walks order by: the bits of a float >= +0 order like the
+// values, and ties go to the lower id. One definition: what is packed here is what every reader takes apart.
+__device__ __forceinline__ unsigned long long queryKey(uint32_t valueBits, int q)
+{
+	return ((unsigned long long)valueBits << 32) | (uint32_t)q;
+}
+__device__ __forceinline__ float queryKeyValue(unsigned long long key) { return __uint_as_float((uint32_t)(key >> 32)); }
+__device__ __forceinline__ int queryKeyFixture(unsigned long long key) { return (int)(uint32_t)key; }
+
+// item k of a list call's flat output belongs to the last query i with offsets[i] <= k (a search over offsets[0 .. n]; empty
+// queries share an offset with the next one)
+__device__ __forceinline__ int queryOwner(const int* offsets, int n, int k)
+{
+	int lo = 0, hi = n; // (offsets[lo] <= k < offsets[hi])
+	while (hi - lo > 1)
+	{
+		const int mid = (lo + hi) >> 1;
+		if (offsets[mid] <= k) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
+// The records of a query that found nothing, every field set (pad included): what the kernels write for a miss and what
+// the host writes for every query of an empty world, where no kernel runs - the same bytes.
+__host__ __device__ inline b2hip_ray_hit queryRayMiss()
+{
+	b2hip_ray_hit o;
+	o.fixture = o.body = -1;
+	o.point_x = o.point_y = o.normal_x = o.normal_y = 0.0f;
+	o.fraction = 1.0f;
+	o.pad = 0;
+	return o;
+}
+__host__ __device__ inline b2hip_distance_hit queryDistanceMiss()
+{
+	b2hip_distance_hit o;
+	o.fixture = o.body = -1;
+	o.point_ax = o.point_ay = o.point_bx = o.point_by = 0.0f;
+	o.distance = INFINITY;
+	o.iterations = 0;
+	return o;
 }
 
 // Calls visit(valid, proxy, fatAabb) for every grid-sized proxy binned in a cell of box's window, 64 candidates per call,
@@ -184,9 +232,9 @@ __device__ __forceinline__ b2hip_distance_hit queryDistanceRecord(const DW& W, i
 // Box, point and shape queries. pass 0: counts[i] = items of query i; pass 1: query i's items (fixture ids, unsorted) at
 // items[offsets[i] ...]. QUERY_POINT: boxes[i] = (x, y, x, y) and the shape must contain the point (b2dShapeTestPoint).
 // QUERY_SHAPE: the box is the query shape's AABB at its pose (b2Shape::ComputeAABB), computed by every lane from the
-// table, and a candidate must overlap the shape (b2TestOverlap: GJK distance with radii from a zeroed cache below
-// 10 epsilon; the query shape is proxy A, as in b2TestOverlap(query, 0, fixture, child, xfQ, xfBody)). Both proxies point
-// into global memory (W.shapes, the query table), so b2dSupport's run-time indexing stays out of scratch.
+// table, and a candidate must overlap the shape (b2TestOverlap: queryDistance below 10 epsilon; the query shape is proxy A,
+// as in b2TestOverlap(query, 0, fixture, child, xfQ, xfBody)). Both proxies point into global memory (W.shapes, the query
+// table), so b2dSupport's run-time indexing stays out of scratch.
 // QUERY_RANGE (b2hip_query_shapes_within): the same box grown by the record's max_distance (QueryPose::tx) on every side, one
 // float operation per coordinate, and a candidate counts when that GJK distance is <= max_distance (queryDistance, the
 // value k_query_range_eval reports afterwards). A pose that is not finite, or a range that is NaN, negative or infinite:
@@ -241,16 +289,7 @@ __device__ __forceinline__ void queryBoxesWave(DW W, const float4* boxes, const 
 				f.hi = v2(fat.z, fat.w);
 				hit = b2dAabbOverlap(a, f) && queryFilterPasses(W, q, mask, sensors);
 				if (KIND == QUERY_POINT && hit) hit = b2dShapeTestPoint(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), a.lo);
-				if (KIND == QUERY_SHAPE && hit)
-				{
-					GjkCache cache;
-					cache.count = 0;
-					cache.metric = 0.0f;
-					for (int k = 0; k < 3; ++k) cache.indexA[k] = cache.indexB[k] = 0;
-					GjkOutput dist;
-					b2dDistance(dist, cache, pQ, xfQ, b2dProxy(W.shapes + W.p_shape[q]), loadXf(W.b_xf, W.p_body[q]), true);
-					hit = dist.distance < 10.0f * B2D_EPSILON;
-				}
+				if (KIND == QUERY_SHAPE && hit) hit = queryDistance(W, q, pQ, xfQ).distance < 10.0f * B2D_EPSILON;
 				if (KIND == QUERY_RANGE && hit) hit = queryDistance(W, q, pQ, xfQ).distance <= range;
 			}
 			const unsigned long long m = __ballot(hit);
@@ -426,16 +465,6 @@ __global__ __launch_bounds__(1024) void k_query_compact_big(int* flags, int nPro
 	}
 }
 
-// Closest ray hit, one WAVE per ray. The ray is cut into pieces about a cell long; the cells of a piece's box (grown by
-// half the grid limit, gridWindow) hold every grid-sized proxy whose box the piece can meet, so after piece k every hit at
-// a fraction up to its end t1 has been seen: the walk stops once the best fraction is below t1. Large proxies are tested
-// by every ray. A candidate is culled by the segment against its fat AABB (b2DynamicTree::RayCast's two tests, the box
-// grown by a margin that covers rounding: only boxes the reference culls as well), then cast against its shape at the
-// body's transform with maxFraction 1 (the fraction and normal of a hit do not depend on maxFraction). Best = the smallest
-// (fraction bits, fixture id): fractions are >= 0 (a -0.0 enters as +0.0), so their bits order like the values, and ties
-// go to the lower id. A ray of more than QUERY_WINDOW_MAX pieces (or with a coordinate beyond QUERY_COORD_MAX) tests every
-// proxy of the world from its one wave instead: 10^6 candidates on a 10^6-body world - a scan is still cheaper than
-// thousands of pieces, but it is the slow case of this kernel.
 __device__ __forceinline__ unsigned long long waveMinU64(unsigned long long v)
 {
 	for (int off = 32; off > 0; off >>= 1)
@@ -465,89 +494,137 @@ __device__ __forceinline__ b2hip_ray_hit queryRayRecord(const DW& W, int q, V2 p
 	return o;
 }
 
+// A walk in pieces about a cell long (rays, and the translation of a shape cast): how many pieces a length takes - 0: more
+// than QUERY_WINDOW_MAX, the caller scans every proxy instead - and the fractions [t0, t1] of piece k. The last piece ends at
+// 1 exactly, and a piece's t1 is the next piece's t0 to the bit: the same division of the same integers.
+__device__ __forceinline__ int queryPieceCount(const DW& W, float len)
+{
+	const float pieces = ceilf(len / gridCell(W));
+	if (!(pieces <= (float)QUERY_WINDOW_MAX)) return 0;
+	return pieces < 1.0f ? 1 : (int)pieces;
+}
+__device__ __forceinline__ void queryPieceSpan(int k, int np, float* t0, float* t1)
+{
+	*t0 = (float)k / (float)np;
+	*t1 = k + 1 == np ? 1.0f : (float)(k + 1) / (float)np;
+}
+
+// One ray of a batch, set up once from its float4, and the ONLY text of the ray walk's arithmetic: k_query_rays (closest)
+// and queryRayHitsWave (all hits, any hit) both cull their candidates by cull() and cut the ray by pieceCount() / piece(), and
+// keep no expression of their own. That is what makes their answers agree to the bit - b2hip_ray_cast_all's first record of
+// a ray IS b2hip_ray_cast_closest's, any == (closest hits something) - also for a ray that grazes a fat box at a piece
+// boundary: both walks see the same boxes, the same margins and the same t0 / t1. The build contracts nothing
+// (-ffp-contract=off), so an expression rounds the same wherever it is inlined; an edit here moves both walks together.
+// Only `valid` means anything for a ray that is not valid (a zero length leaves NaN in perp): test it before any other use.
+struct QueryRay
+{
+	V2 p1, p2, d;
+	bool valid;     // finite and not of zero length: anything else hits nothing
+	float mag, eps; // the largest coordinate; the margin that covers rounding, growing with it
+	float len;
+	V2 perp, aperp; // the unit normal of the ray, and its absolute value
+	V2 slo, shi;    // the ray's own box, grown by eps
+
+	__device__ __forceinline__ explicit QueryRay(float4 r)
+	{
+		p1 = v2(r.x, r.y);
+		p2 = v2(r.z, r.w);
+		d = p2 - p1;
+		valid = isfinite(r.x) && isfinite(r.y) && isfinite(r.z) && isfinite(r.w) && (d.x != 0.0f || d.y != 0.0f);
+		mag = fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fmaxf(fabsf(r.z), fabsf(r.w)));
+		eps = 1.0e-3f + 1.0e-5f * mag;
+		len = sqrtf(d.x * d.x + d.y * d.y);
+		const V2 u = v2(d.x / len, d.y / len);
+		perp = v2(-u.y, u.x);
+		aperp = v2(fabsf(perp.x), fabsf(perp.y));
+		slo = v2(fminf(p1.x, p2.x) - eps, fminf(p1.y, p2.y) - eps);
+		shi = v2(fmaxf(p1.x, p2.x) + eps, fmaxf(p1.y, p2.y) + eps);
+	}
+
+	// true: the segment cannot meet the fat box - the boxes apart, then the ray's normal as a separating axis (k_query_rays)
+	__device__ __forceinline__ bool cull(float4 fat) const
+	{
+		if (fat.x > shi.x || fat.y > shi.y || slo.x > fat.z || slo.y > fat.w) return true;
+		const V2 c = v2(0.5f * (fat.x + fat.z), 0.5f * (fat.y + fat.w));
+		const V2 h = v2(0.5f * (fat.z - fat.x) + eps, 0.5f * (fat.w - fat.y) + eps);
+		const V2 rel = p1 - c;
+		return !(fabsf(perp.x * rel.x + perp.y * rel.y) - (aperp.x * h.x + aperp.y * h.y) <= 0.0f);
+	}
+
+	// how many pieces the walk takes; 0: too many, or a coordinate beyond QUERY_COORD_MAX - every proxy is scanned instead
+	__device__ __forceinline__ int pieceCount(const DW& W) const
+	{
+		const int np = queryPieceCount(W, len);
+		return mag <= QUERY_COORD_MAX ? np : 0;
+	}
+
+	// piece k of np: its fractions and its box, grown by eps; the last piece ends at p2 itself
+	__device__ __forceinline__ float4 piece(int k, int np, float* t0, float* t1) const
+	{
+		queryPieceSpan(k, np, t0, t1);
+		const V2 a = p1 + *t0 * d, b = k + 1 == np ? p2 : p1 + *t1 * d;
+		return make_float4(fminf(a.x, b.x) - eps, fminf(a.y, b.y) - eps, fmaxf(a.x, b.x) + eps, fmaxf(a.y, b.y) + eps);
+	}
+};
+
+// Closest ray hit, one WAVE per ray. The ray is cut into pieces about a cell long; the cells of a piece's box (grown by
+// half the grid limit, gridWindow) hold every grid-sized proxy whose box the piece can meet, so after piece k every hit at
+// a fraction up to its end t1 has been seen: the walk stops once the best fraction is below t1. Large proxies are tested
+// by every ray. A candidate is culled by the segment against its fat AABB (b2DynamicTree::RayCast's two tests, the box
+// grown by a margin that covers rounding: only boxes the reference culls as well), then cast against its shape at the
+// body's transform with maxFraction 1 (the fraction and normal of a hit do not depend on maxFraction). Best = the smallest
+// (fraction bits, fixture id): fractions are >= 0 (a -0.0 enters as +0.0), so their bits order like the values, and ties
+// go to the lower id. A ray of more than QUERY_WINDOW_MAX pieces (or with a coordinate beyond QUERY_COORD_MAX) tests every
+// proxy of the world from its one wave instead: 10^6 candidates on a 10^6-body world - a scan is still cheaper than
+// thousands of pieces, but it is the slow case of this kernel.
 __global__ __launch_bounds__(256) void k_query_rays(DW W, const float4* rays, int n, uint32_t mask, int sensors, b2hip_ray_hit* out)
 {
 	const int lane = (int)(threadIdx.x & 63u);
 	const int nWaves = (int)((gridDim.x * blockDim.x) >> 6);
 	for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nWaves)
 	{
-		const float4 r = rays[i];
-		const V2 p1 = v2(r.x, r.y), p2 = v2(r.z, r.w);
-		const V2 d = p2 - p1;
+		const QueryRay ray(rays[i]);
 		unsigned long long best = ~0ull;
-		const bool finite = isfinite(r.x) && isfinite(r.y) && isfinite(r.z) && isfinite(r.w);
-		if (finite && (d.x != 0.0f || d.y != 0.0f))
+		if (ray.valid)
 		{
-			const float mag = fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fmaxf(fabsf(r.z), fabsf(r.w)));
-			const float eps = 1.0e-3f + 1.0e-5f * mag;
-			const float len = sqrtf(d.x * d.x + d.y * d.y);
-			const V2 u = v2(d.x / len, d.y / len);
-			const V2 perp = v2(-u.y, u.x), aperp = v2(fabsf(perp.x), fabsf(perp.y));
-			const V2 slo = v2(fminf(p1.x, p2.x) - eps, fminf(p1.y, p2.y) - eps);
-			const V2 shi = v2(fmaxf(p1.x, p2.x) + eps, fmaxf(p1.y, p2.y) + eps);
 			auto visit = [&](bool valid, int q, float4 fat)
 			{
-				bool cand = valid && !(fat.x > shi.x || fat.y > shi.y || slo.x > fat.z || slo.y > fat.w);
-				if (cand)
-				{
-					const V2 c = v2(0.5f * (fat.x + fat.z), 0.5f * (fat.y + fat.w));
-					const V2 h = v2(0.5f * (fat.z - fat.x) + eps, 0.5f * (fat.w - fat.y) + eps);
-					const V2 rel = p1 - c;
-					cand = fabsf(perp.x * rel.x + perp.y * rel.y) - (aperp.x * h.x + aperp.y * h.y) <= 0.0f;
-				}
-				if (cand) cand = queryFilterPasses(W, q, mask, sensors);
-				if (cand)
+				if (valid && !ray.cull(fat) && queryFilterPasses(W, q, mask, sensors))
 				{
 					RayHit hit;
-					if (b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), p1, p2, 1.0f, &hit))
+					if (b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), ray.p1, ray.p2, 1.0f, &hit))
 					{
 						// (+ 0.0f: a ray that starts on an edge or a circle is hit at -0.0, whose bits would sort after
 						// every positive fraction; the kept hit's own fraction, -0.0 included, is reported below)
-						const unsigned long long key = ((unsigned long long)__float_as_uint(hit.fraction + 0.0f) << 32) | (uint32_t)q;
+						const unsigned long long key = queryKey(__float_as_uint(hit.fraction + 0.0f), q);
 						best = key < best ? key : best;
 					}
 				}
 			};
 			queryVisitLarge(W, lane, visit);
-			const float cell = gridCell(W);
-			const float pieces = ceilf(len / cell);
-			bool all = !(pieces <= (float)QUERY_WINDOW_MAX) || !(mag <= QUERY_COORD_MAX);
-			if (!all)
+			const int np = ray.pieceCount(W);
+			bool all = np == 0;
+			for (int k = 0; k < np; ++k)
 			{
-				const int np = pieces < 1.0f ? 1 : (int)pieces;
-				for (int k = 0; k < np; ++k)
+				float t0, t1;
+				if (!queryVisitGrid(W, lane, ray.piece(k, np, &t0, &t1), visit))
 				{
-					const float t0 = (float)k / (float)np, t1 = k + 1 == np ? 1.0f : (float)(k + 1) / (float)np;
-					const V2 a = p1 + t0 * d, b = k + 1 == np ? p2 : p1 + t1 * d;
-					const float4 box = make_float4(fminf(a.x, b.x) - eps, fminf(a.y, b.y) - eps, fmaxf(a.x, b.x) + eps, fmaxf(a.y, b.y) + eps);
-					if (!queryVisitGrid(W, lane, box, visit))
-					{
-						all = true;
-						break;
-					}
-					best = waveMinU64(best);
-					if (best != ~0ull && __uint_as_float((uint32_t)(best >> 32)) < t1) break;
+					all = true;
+					break;
 				}
+				best = waveMinU64(best);
+				if (best != ~0ull && queryKeyValue(best) < t1) break;
 			}
 			if (all) queryVisitAll(W, lane, visit);
 			best = waveMinU64(best);
 		}
-		if (lane == 0)
-		{
-			b2hip_ray_hit o;
-			o.fixture = -1;
-			o.body = -1;
-			o.point_x = o.point_y = o.normal_x = o.normal_y = 0.0f;
-			o.fraction = 1.0f;
-			o.pad = 0;
-			if (best != ~0ull) o = queryRayRecord(W, (int)(uint32_t)best, p1, p2); // (the kept hit again: its normal)
-			out[i] = o;
-		}
+		// (the kept hit again: its normal)
+		if (lane == 0) out[i] = best != ~0ull ? queryRayRecord(W, queryKeyFixture(best), ray.p1, ray.p2) : queryRayMiss();
 	}
 }
 
 // Every hit of a ray (b2hip_ray_cast_all) and whether there is one (b2hip_ray_cast_any), one WAVE per ray, walked and culled
-// as k_query_rays does (the same expressions: a piece's t1 is the next piece's t0 to the bit). MODE QUERY_RAY_COUNT:
+// by the QueryRay that k_query_rays walks (one text: a piece's t1 is the next piece's t0 to the bit). MODE QUERY_RAY_COUNT:
 // counts[i] = hits of ray i; QUERY_RAY_FILL: their keys (bits of fraction + 0.0f) << 32 | fixture id, unsorted, at
 // keys[offsets[i] ...]; QUERY_RAY_ANY: any[i] = 1 when something is hit.
 // Once only: the windows of successive pieces overlap (gridWindow grows a piece's box by half the grid limit), so a grid-sized
@@ -572,41 +649,21 @@ __device__ __forceinline__ void queryRayHitsWave(DW W, const float4* rays, int n
 	const int nWaves = (int)((gridDim.x * blockDim.x) >> 6);
 	for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nWaves)
 	{
-		const float4 r = rays[i];
-		const V2 p1 = v2(r.x, r.y), p2 = v2(r.z, r.w);
-		const V2 d = p2 - p1;
+		const QueryRay ray(rays[i]);
 		int found = 0;
-		const bool finite = isfinite(r.x) && isfinite(r.y) && isfinite(r.z) && isfinite(r.w);
-		if (finite && (d.x != 0.0f || d.y != 0.0f))
+		if (ray.valid)
 		{
-			const float mag = fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fmaxf(fabsf(r.z), fabsf(r.w)));
-			const float eps = 1.0e-3f + 1.0e-5f * mag;
-			const float len = sqrtf(d.x * d.x + d.y * d.y);
-			const V2 u = v2(d.x / len, d.y / len);
-			const V2 perp = v2(-u.y, u.x), aperp = v2(fabsf(perp.x), fabsf(perp.y));
-			const V2 slo = v2(fminf(p1.x, p2.x) - eps, fminf(p1.y, p2.y) - eps);
-			const V2 shi = v2(fmaxf(p1.x, p2.x) + eps, fmaxf(p1.y, p2.y) + eps);
 			const int at = MODE == QUERY_RAY_FILL ? offsets[i] : 0, end = MODE == QUERY_RAY_FILL ? offsets[i + 1] : 0;
 			float t0 = 0.0f, t1 = 1.0f; // a hit counts when t0 <= fraction + 0.0f < t1 - or <= t1 when `closed`
 			bool closed = true;
 			auto visit = [&](bool valid, int q, float4 fat)
 			{
-				bool cand = valid && !(MODE == QUERY_RAY_ANY && found > 0);
-				cand = cand && !(fat.x > shi.x || fat.y > shi.y || slo.x > fat.z || slo.y > fat.w);
-				if (cand)
-				{
-					const V2 c = v2(0.5f * (fat.x + fat.z), 0.5f * (fat.y + fat.w));
-					const V2 h = v2(0.5f * (fat.z - fat.x) + eps, 0.5f * (fat.w - fat.y) + eps);
-					const V2 rel = p1 - c;
-					cand = fabsf(perp.x * rel.x + perp.y * rel.y) - (aperp.x * h.x + aperp.y * h.y) <= 0.0f;
-				}
-				if (cand) cand = queryFilterPasses(W, q, mask, sensors);
 				bool hit = false;
 				float f = 0.0f;
-				if (cand)
+				if (valid && !(MODE == QUERY_RAY_ANY && found > 0) && !ray.cull(fat) && queryFilterPasses(W, q, mask, sensors))
 				{
 					RayHit rh;
-					if (b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), p1, p2, 1.0f, &rh))
+					if (b2dShapeRayCast(W.shapes + W.p_shape[q], loadXf(W.b_xf, W.p_body[q]), ray.p1, ray.p2, 1.0f, &rh))
 					{
 						f = rh.fraction + 0.0f; // (a -0.0 enters as +0.0, as in k_query_rays)
 						hit = MODE == QUERY_RAY_ANY || (f >= t0 && (f < t1 || closed));
@@ -616,29 +673,20 @@ __device__ __forceinline__ void queryRayHitsWave(DW W, const float4* rays, int n
 				if (MODE == QUERY_RAY_FILL && hit)
 				{
 					const int k = at + found + (int)__popcll(m & ((1ull << lane) - 1ull));
-					if (k < end) keys[k] = ((unsigned long long)__float_as_uint(f) << 32) | (uint32_t)q;
+					if (k < end) keys[k] = queryKey(__float_as_uint(f), q);
 				}
 				found += (int)__popcll(m);
 			};
-			const float cell = gridCell(W);
-			const float pieces = ceilf(len / cell);
-			bool all = !(pieces <= (float)QUERY_WINDOW_MAX) || !(mag <= QUERY_COORD_MAX);
-			if (!all)
+			const int np = ray.pieceCount(W);
+			bool all = np == 0;
+			if (!all) queryVisitLarge(W, lane, visit);
+			for (int k = 0; k < np && !(MODE == QUERY_RAY_ANY && found > 0); ++k)
 			{
-				queryVisitLarge(W, lane, visit);
-				const int np = pieces < 1.0f ? 1 : (int)pieces;
-				for (int k = 0; k < np && !(MODE == QUERY_RAY_ANY && found > 0); ++k)
+				closed = k + 1 == np;
+				if (!queryVisitGrid(W, lane, ray.piece(k, np, &t0, &t1), visit))
 				{
-					t0 = (float)k / (float)np;
-					t1 = k + 1 == np ? 1.0f : (float)(k + 1) / (float)np;
-					closed = k + 1 == np;
-					const V2 a = p1 + t0 * d, b = k + 1 == np ? p2 : p1 + t1 * d;
-					const float4 box = make_float4(fminf(a.x, b.x) - eps, fminf(a.y, b.y) - eps, fmaxf(a.x, b.x) + eps, fmaxf(a.y, b.y) + eps);
-					if (!queryVisitGrid(W, lane, box, visit))
-					{
-						all = true;
-						break;
-					}
+					all = true;
+					break;
 				}
 			}
 			if (all)
@@ -672,21 +720,15 @@ __global__ __launch_bounds__(256) void k_query_rays_any(DW W, const float4* rays
 	queryRayHitsWave<QUERY_RAY_ANY>(W, rays, n, mask, sensors, nullptr, nullptr, nullptr, any);
 }
 
-// The records of b2hip_ray_cast_all, after the sort: one thread per key. Key k belongs to the last ray i with
-// offsets[i] <= k (as k_query_range_eval finds its query); its fixture is cast again and the record written out whole.
+// The records of b2hip_ray_cast_all, after the sort: one thread per key. Key k belongs to ray queryOwner(k); its fixture is
+// cast again and the record written out whole.
 __global__ __launch_bounds__(256) void k_query_rays_all_eval(DW W, const float4* rays, int n, const int* offsets, const unsigned long long* keys,
                                                              int nItems, b2hip_ray_hit* out)
 {
 	for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < nItems; k += (int)(gridDim.x * blockDim.x))
 	{
-		int lo = 0, hi = n; // (offsets[lo] <= k < offsets[hi])
-		while (hi - lo > 1)
-		{
-			const int mid = (lo + hi) >> 1;
-			if (offsets[mid] <= k) lo = mid; else hi = mid;
-		}
-		const float4 r = rays[lo];
-		out[k] = queryRayRecord(W, (int)(uint32_t)keys[k], v2(r.x, r.y), v2(r.z, r.w));
+		const float4 r = rays[queryOwner(offsets, n, k)];
+		out[k] = queryRayRecord(W, queryKeyFixture(keys[k]), v2(r.x, r.y), v2(r.z, r.w));
 	}
 }
 
@@ -734,7 +776,7 @@ __global__ __launch_bounds__(256) void k_query_shape_casts(DW W, const QueryPose
 					ShapeCastResult r;
 					if (b2dShapeCast(&r, b2dProxy(W.shapes + W.p_shape[q]), loadXf(W.b_xf, W.p_body[q]), pB, xfB, t))
 					{
-						const unsigned long long key = ((unsigned long long)__float_as_uint(r.lambda + 0.0f) << 32) | (uint32_t)q;
+						const unsigned long long key = queryKey(__float_as_uint(r.lambda + 0.0f), q);
 						best = key < best ? key : best;
 					}
 				}
@@ -745,14 +787,14 @@ __global__ __launch_bounds__(256) void k_query_shape_casts(DW W, const QueryPose
 			if (!all && !queryVisitGrid(W, lane, whole, visit))
 			{
 				const float len = sqrtf(t.x * t.x + t.y * t.y);
-				const float pieces = ceilf(len / gridCell(W));
-				all = !(pieces <= (float)QUERY_WINDOW_MAX);
+				const int np = queryPieceCount(W, len);
+				all = np == 0;
 				if (!all)
 				{
-					const int np = pieces < 1.0f ? 1 : (int)pieces;
 					for (int k = 0; k < np; ++k)
 					{
-						const float t0 = (float)k / (float)np, t1 = k + 1 == np ? 1.0f : (float)(k + 1) / (float)np;
+						float t0, t1;
+						queryPieceSpan(k, np, &t0, &t1);
 						const V2 a = t0 * t, b = t1 * t;
 						const float4 box = make_float4(box0.lo.x + fminf(a.x, b.x) - margin, box0.lo.y + fminf(a.y, b.y) - margin,
 						                               box0.hi.x + fmaxf(a.x, b.x) + margin, box0.hi.y + fmaxf(a.y, b.y) + margin);
@@ -762,7 +804,7 @@ __global__ __launch_bounds__(256) void k_query_shape_casts(DW W, const QueryPose
 							break;
 						}
 						best = waveMinU64(best);
-						if (best != ~0ull && __uint_as_float((uint32_t)(best >> 32)) < t1) break;
+						if (best != ~0ull && queryKeyValue(best) < t1) break;
 					}
 				}
 			}
@@ -771,15 +813,10 @@ __global__ __launch_bounds__(256) void k_query_shape_casts(DW W, const QueryPose
 		}
 		if (lane == 0)
 		{
-			b2hip_ray_hit o;
-			o.fixture = -1;
-			o.body = -1;
-			o.point_x = o.point_y = o.normal_x = o.normal_y = 0.0f;
-			o.fraction = 1.0f;
-			o.pad = 0;
+			b2hip_ray_hit o = queryRayMiss();
 			if (best != ~0ull)
 			{
-				const int q = (int)(uint32_t)best;
+				const int q = queryKeyFixture(best);
 				const int body = W.p_body[q];
 				ShapeCastResult r;
 				(void)b2dShapeCast(&r, b2dProxy(W.shapes + W.p_shape[q]), loadXf(W.b_xf, body), pB, xfB, t); // (the kept hit again)
@@ -797,20 +834,13 @@ __global__ __launch_bounds__(256) void k_query_shape_casts(DW W, const QueryPose
 }
 
 // The records of b2hip_query_shapes_within, after the sort (it moves bare fixture ids): one thread per item. Item k belongs
-// to the last query i with offsets[i] <= k (a search over offsets[0 .. n]; empty queries share an offset with the next one);
-// its distance is computed again, as the fill pass computed it, and written out whole.
+// to query queryOwner(k); its distance is computed again, as the fill pass computed it, and written out whole.
 __global__ __launch_bounds__(256) void k_query_range_eval(DW W, const QueryPose* poses, const ShapeRec* qshapes, int n, const int* offsets,
                                                           const int* items, int nItems, b2hip_distance_hit* out)
 {
 	for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < nItems; k += (int)(gridDim.x * blockDim.x))
 	{
-		int lo = 0, hi = n; // (offsets[lo] <= k < offsets[hi])
-		while (hi - lo > 1)
-		{
-			const int mid = (lo + hi) >> 1;
-			if (offsets[mid] <= k) lo = mid; else hi = mid;
-		}
-		const QueryPose qp = poses[lo];
+		const QueryPose qp = poses[queryOwner(offsets, n, k)];
 		out[k] = queryDistanceRecord(W, items[k], b2dProxy(qshapes + qp.shape), queryPoseXf(qp));
 	}
 }
@@ -858,7 +888,7 @@ __global__ __launch_bounds__(256) void k_query_shape_distances(DW W, const Query
 					const float dist = queryDistance(W, q, pQ, xfQ).distance;
 					if (dist <= range)
 					{
-						const unsigned long long key = ((unsigned long long)__float_as_uint(dist) << 32) | (uint32_t)q;
+						const unsigned long long key = queryKey(__float_as_uint(dist), q);
 						best = key < best ? key : best;
 					}
 				}
@@ -877,7 +907,7 @@ __global__ __launch_bounds__(256) void k_query_shape_distances(DW W, const Query
 						break;
 					}
 					best = waveMinU64(best);
-					if (last || (best != ~0ull && __uint_as_float((uint32_t)(best >> 32)) < r - margin)) break;
+					if (last || (best != ~0ull && queryKeyValue(best) < r - margin)) break;
 					done = box;
 				}
 			}
@@ -886,14 +916,8 @@ __global__ __launch_bounds__(256) void k_query_shape_distances(DW W, const Query
 		}
 		if (lane == 0)
 		{
-			b2hip_distance_hit o;
-			o.fixture = -1;
-			o.body = -1;
-			o.point_ax = o.point_ay = o.point_bx = o.point_by = 0.0f;
-			o.distance = __uint_as_float(0x7f800000u);
-			o.iterations = 0;
-			if (best != ~0ull) o = queryDistanceRecord(W, (int)(uint32_t)best, pQ, xfQ); // (the kept candidate again)
-			out[i] = o;
+			// (the kept candidate again)
+			out[i] = best != ~0ull ? queryDistanceRecord(W, queryKeyFixture(best), pQ, xfQ) : queryDistanceMiss();
 		}
 	}
 }

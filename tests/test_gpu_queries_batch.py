@@ -404,3 +404,30 @@ def test_a_ray_that_starts_on_an_edge(amd):
     assert ray_matches(rows, hit, r) == "same"
     dw.close()
     hw.close()
+
+
+@pytest.mark.gpu
+def test_misses_are_the_same_bytes_from_the_host_and_from_the_device():
+    """An empty world runs no kernel: the host writes the miss records. A world of one box queried 1 000 m away runs the
+    kernels, which write theirs. One definition serves both (queryRayMiss / queryDistanceMiss): the same bytes."""
+    empty = b2hip.World()
+    far = b2hip.World()
+    far.create_fixture(far.create_body(b2hip.STATIC, (0.0, 0.0)), b2hip.box_shape(0.5, 0.5))
+    far.step()
+    p1 = np.array([[1000.0, 0.0], [0.0, 1000.0], [-1000.0, -1000.0]], np.float32)
+    p2 = p1 + np.float32([1.0, 0.5])
+    poses = np.concatenate([p1, np.float32([[0.0], [0.7], [-2.0]])], axis=1)
+    moves = np.array([[1.0, 0.0], [0.0, -1.0], [0.5, 0.5]], np.float32)
+    circle = b2hip.circle_shape(0.25)
+    got = []
+    for w in (empty, far):
+        fixed = [w.ray_cast_closest(p1, p2), w.shape_cast_closest(circle, poses, moves), w.shape_distance_closest(circle, poses, 1.0)]
+        assert all(len(r) == 3 and np.all(r["fixture"] == -1) for r in fixed)
+        assert not w.ray_cast_any(p1, p2).any()
+        lists = [w.query_aabbs(p1, p2), w.query_points(p1), w.ray_cast_all(p1, p2), w.query_shapes(circle, poses),
+                 w.query_shapes_within(circle, poses, 1.0)]
+        for offs, items in lists:
+            assert offs.tolist() == [0, 0, 0, 0] and len(items) == 0
+        got.append([r.tobytes() for r in fixed])
+        w.close()
+    assert got[0] == got[1]
