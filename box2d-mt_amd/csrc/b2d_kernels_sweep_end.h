@@ -710,7 +710,7 @@ __global__ __launch_bounds__(SWEEP_END_LANES) void k_rest_hub(DW W, StepParams s
 	sweepEndBody<MODE>(W, sp, 0, 0, what, stampBar, &rj);
 }
 
-// ---- a solve that can be run again (round 6; b2hip_host_phases.h: runLarge) ----------------------------------------------------------
+// ---- a solve that can be run again (round 6; b2hip_host_phases.h: LargePass) ----------------------------------------------------------
 // What the large-island solver CHANGES, saved before its first launch and put back if a wait between its workgroups timed
 // out: the rows of the large islands' bodies (position + sleep time, sweep start, velocity, transform, flags, force), the
 // impulses and flags of their contacts, their joints (accumulated impulses, per-step scratch). Everything else the solver

@@ -372,8 +372,7 @@ struct SolveStep
 	bool useSweep = false;            // k_blocks_sweep (else a launch per colour)
 	bool colorsOnDevice = false;      // k_solve_blocks reads the colour count on the device
 	bool censusVoid = false;          // colours were handed out afresh: the colour census of this step is history
-	bool colorSpill = false;          // some constraint found no free colour this step: it sits in the hub group and is swept in order
-	bool waitsBetweenWorkgroups = false; // the solve used a kernel whose workgroups wait for one another
+	bool colorSpill = false;          // some constraint found no free colour this step: it sits in the hub group (k_hub_flag lists it; hasHubs is set with it) and is swept in order
 };
 
 static const int RECOLOR_SLACK = 2; // colour afresh when the colours in use exceed the last fresh colouring's by more than this
@@ -711,7 +710,7 @@ static int colorRoundsUntilDone(b2hip_world* w, SolveStep& s, int uncolored, int
 		if (int rc = readState(w)) return rc;
 		uncolored = w->h_dstate->c.nUncolored;
 		s.nColors = w->h_dstate->c.nColors;
-		if (w->h_dstate->c.overflow & 4) { if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "more than 64 constraint colours on one body"); s.colorSpill = true; }
+		if (w->h_dstate->c.overflow & 4) { if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "more than 64 constraint colours on one body"); s.colorSpill = s.hasHubs = true; }
 	}
 	return 0;
 }
@@ -752,7 +751,7 @@ static int colorLargeIslands(b2hip_world* w, SolveStep& s)
 		s.nColors = w->h_dstate->c.nColors;
 		// (round 6: neither ends the step any more. A constraint without a free colour on its two bodies is swept in order
 		// with the hub rows - k_hub_flag; rounds that did not converge are finished by the grid-wide rounds below)
-		if (w->h_dstate->c.overflow & 4) { if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "more than 64 constraint colours on one body"); s.colorSpill = true; }
+		if (w->h_dstate->c.overflow & 4) { if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "more than 64 constraint colours on one body"); s.colorSpill = s.hasHubs = true; }
 		if (w->h_dstate->c.nUncolored == 0) return 0;
 		if (!w->recoverOn) return setError(B2HIP_ERR_CAPACITY, "incremental colouring did not converge");
 		c.nUncolored = w->h_dstate->c.nUncolored;
@@ -784,6 +783,121 @@ static int wipeHandoverRows(b2hip_world* w)
 	return 0;
 }
 
+// Every decision of one pass of the large-island solve, made before its first launch (planLargePass) and read by the stages
+// of LargePass: none depends on what a launch of the pass produces.
+struct LargePlan
+{
+	bool safe = false;            // the second pass of a recovered step: no rest flow, no snapshot, no timing-mode-5 record
+	bool useSweepEnd = false;     // sweeps end in k_sweep_end / k_rest_hub (else k_large_hub, k_large_joints, k_large_pos_end apart)
+	int restFirst = 0x7fffffff;   // colours [restFirst, nColors) are the rest colours of k_large_rest (0x7fffffff: none)
+	long long restRows = 0;       // an upper bound of their rows: sizes the grids of k_large_rest and k_rest_hub
+	bool useRest = false;         // there are rest colours (only where the rows lie by colour: never beside k_blocks_sweep)
+	int tailFirst = 0;            // colours [tailFirst, nColors) are swept inside k_sweep_end (the rest colours' start with useRest)
+	bool tailAny = false;         // ... and one of them owns a constraint
+	int bigEnd = 0;               // colours [0, bigEnd) are launches of their own
+	bool leftoverApart = false;   // the hub rows behind the fixed point go to k_large_hub between two launches of k_sweep_end
+	bool fuseHub = false;         // k_large_rest and k_sweep_end of one sweep as ONE launch, k_rest_hub
+	bool bodyWarm = false;        // the warm start body by body in one launch, k_large_warm
+	bool hubBuildOne = false;     // the hub list by one launch of k_hub_build (else k_hub_flag, scan, k_hub_fill, k_hub_order)
+	bool sortInIntegrate = false; // k_large_integrate sorts the joints of every island too (else k_joints_sort apart)
+	bool afterFused = false;      // k_large_after_velocity (else impulses stored, positions integrated, k_large_pos_begin apart)
+	bool censusGrid = false;      // colour launches are sized from this step's colour census (else all alike: gK)
+	uint64_t colorMask = ~0ull;   // bit per colour below 64: it owns a constraint
+	int gB = 0, gC = 0, gJ = 0;   // grids over the large islands' bodies, their contacts, the islands themselves (joint walks)
+	int gK = 0;                   // grid of a colour launch sized from the mean colour
+	bool waitsBetweenWorkgroups = false; // the pass uses a kernel whose workgroups wait for one another: snapshot before, look behind
+};
+
+static inline bool colorUsed(const LargePlan& p, int col) { return col >= 64 || ((p.colorMask >> col) & 1ull) != 0; }
+
+// The plan of one pass from the step, the switches and the census the host holds. Launches nothing. `safe`: the pass that
+// follows a recovery (recoverLarge has taken the solver choice back to a launch per colour).
+static LargePlan planLargePass(const b2hip_world* w, const SolveStep& s, const bool safe)
+{
+	const DW& d = w->dw;
+	const StepParams& sp = w->sp;
+	const Counters& c = s.c;
+	const int nColors = s.nColors;
+	LargePlan p;
+	p.safe = safe;
+	p.gB = gridFor(s.nLBodies);
+	p.gC = gridFor(std::max(s.nLContacts, 1));
+	p.gJ = gridFor(std::max(s.nLIslands, 1), 64, 1 << 16);
+	p.useSweepEnd = w->sweepEnd && !s.exactLarge && !w->debugTrace;
+	// ---- the end of every sweep without a launch per colour (b2d_kernels_sweep_end.h). The REST colours - from the highest
+	// colour down while this step's colour census (k_color_check, published with the island census) keeps them below
+	// restRowsMax rows together - are swept by ONE launch of k_large_rest, as data flow per body; k_color_fill notes them
+	// on their bodies. Which colours are "rest" changes nothing in the result (the order on every body is the launches'):
+	// a launch-count matter. Not on a step that colours afresh: its census is void.
+	if (p.useSweepEnd && w->restFlow && !safe && !d.blockSort && !c.needRecolor && !s.censusVoid && nColors > 0 && nColors < MAX_COLORS)
+	{
+		long long sum = 0;
+		int t = nColors;
+		while (t > 0 && sum + c.colorRows[t - 1] <= (long long)w->restRowsMax)
+		{
+			sum += c.colorRows[t - 1];
+			t -= 1;
+		}
+		if (nColors - t >= 2) p.restFirst = t;
+	}
+	// (the census is this step's before k_color_small handed out its colours - at most COLOR_SMALL_MAX rows more)
+	p.restRows = COLOR_SMALL_MAX;
+	for (int col = p.restFirst; col < nColors && col < MAX_COLORS; ++col) p.restRows += c.colorRows[col];
+	p.useRest = p.useSweepEnd && p.restFirst < nColors;
+	// (round 6: one single-workgroup launch sorts the hub group's segment of the row array in place - k_hub_build - where the
+	// last step's list was short enough for its keys to sit in LDS; the four launches of layoutRows otherwise)
+	p.hubBuildOne = s.hasHubs && !w->noHubBuild && w->last.nHubRows <= HUB_BUILD_LDS;
+	p.gK = gridFor(std::max(s.nLContacts / std::max(nColors, 1), 1) * 2);
+	// A colour launch is a chain of dependent loads per lane (~4.5 us whatever it holds): a lane that makes a second trip
+	// of the grid-stride loop pays the chain twice - the Tumbler's five biggest colours (41 000 - 42 000 rows against a grid
+	// of 39 000 lanes sized from the MEAN colour) took 8 us instead of 6. Sized per colour from this step's census now
+	// (+ what k_color_small may still add), in workgroups of 256 lanes so that the rows spread over all CUs.
+	p.censusGrid = !s.exactLarge && nColors > 0 && nColors <= MAX_COLORS && !c.needRecolor && !s.censusVoid;
+	p.waitsBetweenWorkgroups = s.useBlocks || s.useSweep || p.useRest;
+	p.sortInIntegrate = s.hasJoints && !s.exactLarge && !w->debugTrace;
+	// (the warm start body by body in one launch - k_large_warm - where the sweep would be a launch per colour: k_large_init
+	// leaves the deltas for it)
+	p.bodyWarm = w->bodyWarm && w->sweepEnd && !s.exactLarge && !w->debugTrace && !s.useSweep && sp.warmStarting && nColors <= MAX_COLORS;
+	// colours that own no constraint (the partition keeps two colour ranges apart) are not launched
+	// (the mask of the host's LAST copy: s.c can be an older one once the colours were awaited)
+	p.colorMask = s.exactLarge ? ~0ull : ((uint64_t)w->h_dstate->c.colorMaskLo | ((uint64_t)w->h_dstate->c.colorMaskHi << 32));
+	// ---- the end of every sweep in ONE single-workgroup launch (b2d_kernels_sweep_end.h): the tail colours - those this
+	// step's colour census (k_color_check, published with the island census) found small, from the highest colour down -
+	// the hub rows, the joint walk, the verdict of a position iteration. Which colours are "tail" changes nothing in the
+	// result (k_sweep_end does k_large_velocity's / k_large_position's arithmetic row for row): a pure launch-count matter.
+	p.tailFirst = p.useRest ? p.restFirst : nColors;
+	if (p.useSweepEnd && w->sweepTail && !p.useRest && !s.useSweep && !c.needRecolor && !s.censusVoid && nColors <= MAX_COLORS)
+	{
+		long long sum = 0;
+		while (p.tailFirst > 0 && c.colorRows[p.tailFirst - 1] <= w->tailRowsMax && sum + c.colorRows[p.tailFirst - 1] <= 8ll * w->tailRowsMax)
+		{
+			sum += c.colorRows[p.tailFirst - 1];
+			p.tailFirst -= 1;
+		}
+	}
+	for (int col = p.tailFirst; col < nColors && !p.useRest; ++col) p.tailAny = p.tailAny || colorUsed(p, col);
+	p.bigEnd = s.useSweep ? 0 : p.tailFirst;
+	// The hub rows the one fixed point cannot take are swept lane after lane inside k_sweep_end - a handful on the Tumbler
+	// (boxes in the corners). An island that kept many of them in the LAST step (several hubs, constraints swept in order for
+	// lack of a home block; the census still carries that step's counts) gets k_large_hub's eight prefetching waves for
+	// them: k_sweep_end up to the fixed point, k_large_hub, k_sweep_end for what follows the hub rows. (Either way a valid
+	// sweep; which one is decided from counters a snapshot carries, so a loaded world decides alike.)
+	p.leftoverApart = p.useSweepEnd && s.hasHubs && d.hubWide && c.nHubRows - c.nHubWide > SE_LEFT_INLINE_MAX;
+	// ---- k_large_rest and k_sweep_end of one sweep as ONE launch (k_rest_hub, round 6): the rest rows in gF workgroups of
+	// 512 lanes, the hub rows / joints / verdict in one more that waits for what it needs of them as tagged rows. All
+	// workgroups must be resident together (restHubMaxWG: the occupancy query at world creation).
+	p.fuseHub = p.useRest && w->restHub && (s.hasHubs || s.hasJoints) && !p.leftoverApart && w->restHubMaxWG > 1;
+	// (one launch for the three: k_large_after_velocity; apart where a trace wants to see each)
+	p.afterFused = !w->debugTrace && sp.posIters > 0;
+	return p;
+}
+
+static inline int gridOfColor(const SolveStep& s, const LargePlan& p, int col)
+{
+	if (!p.censusGrid || col < 0 || col >= MAX_COLORS) return p.gK;
+	return gridFor((size_t)s.c.colorRows[col] + 512, 256, 1 << 16);
+}
+
 // ---- the row layout and the solver proper, as ONE unit that can run a second time in its SAFE form (round 6, VERDICT r05
 // item 5): b2World::Step has no failure path (b2World.cpp:1613-1710), and a wait between workgroups that times out - a
 // co-tenant on the device, a workgroup that was not resident - used to fail the step and leave a dead world. The unit
@@ -794,318 +908,279 @@ static int wipeHandoverRows(b2hip_world* w)
 // again on the plain path: rows by colour, a launch per colour, tail colours and hub rows in k_sweep_end's ONE workgroup -
 // nothing in it waits for another workgroup. Same colouring, same arithmetic, same order on every body: the bits the
 // fast path would have produced (tests/test_gpu_recovery.py).
-static int solveLargePass(b2hip_world* w, SolveStep& s, const bool safe)
+// One pass over (w, s, plan): a dispatch per kernel family - from a run-time lane count / mode to the instantiation - and the
+// stages in the order of b2Island::Solve (b2Island.cpp:256-336); run() is the unit.
+struct LargePass
 {
-	DW& d = w->dw;
-	const StepParams& sp = w->sp;
-	const Counters& c = s.c;
-	const int nColors = s.nColors, nLIslands = s.nLIslands, nLBodies = s.nLBodies, nLContacts = s.nLContacts;
-	const bool exactLarge = s.exactLarge, hasJoints = s.hasJoints;
-	int rc = 0;
-	if (safe)
+	b2hip_world* const w;
+	SolveStep& s;
+	const LargePlan p;
+	DW& d;
+	const StepParams& sp;
+	LargePass(b2hip_world* w_, SolveStep& s_, bool safe) : w(w_), s(s_), p(planLargePass(w_, s_, safe)), d(w_->dw), sp(w_->sp) {}
+
+	// Every launch of k_solve_blocks / k_blocks_sweep / k_large_rest / k_rest_hub tags its hand-over rows with an epoch of its own.
+	template <typename Launch>
+	int withEpoch(Launch launch)
 	{
-		s.useBlocks = s.useSweep = false;
-		s.colorsOnDevice = false;
-		d.blockSort = 0;
-	}
-	if (s.colorSpill) s.hasHubs = true; // (k_hub_flag lists the constraints that found no colour)
-	const bool hasHubs = s.hasHubs, useSweep = s.useSweep;
-	const int gB = gridFor(nLBodies), gC = gridFor(std::max(nLContacts, 1));
-	if (!d.blockSort) LAUNCH(w, k_color_scan, 1, 64, d); // (segments by colour: the block solvers sort their rows themselves)
-	// ---- the end of every sweep without a launch per colour (b2d_kernels_sweep_end.h). The REST colours - from the highest
-	// colour down while this step's colour census (k_color_check, published with the island census) keeps them below
-	// restRowsMax rows together - are swept by ONE launch of k_large_rest, as data flow per body; k_color_fill notes them
-	// on their bodies. Which colours are "rest" changes nothing in the result (the order on every body is the launches'):
-	// a launch-count matter. Not on a step that colours afresh: its census is void.
-	const bool useSweepEnd = w->sweepEnd && !exactLarge && !w->debugTrace;
-	int restFirst = 0x7fffffff; // (none)
-	if (useSweepEnd && w->restFlow && !safe && !d.blockSort && !c.needRecolor && !s.censusVoid && nColors > 0 && nColors < MAX_COLORS)
-	{
-		long long sum = 0;
-		int t = nColors;
-		while (t > 0 && sum + c.colorRows[t - 1] <= (long long)w->restRowsMax)
-		{
-			sum += c.colorRows[t - 1];
-			t -= 1;
-		}
-		if (nColors - t >= 2) restFirst = t;
-	}
-	w->lastRestFirst = restFirst < nColors ? restFirst : nColors;
-	// (the census is this step's before k_color_small handed out its colours - at most COLOR_SMALL_MAX rows more)
-	long long restRows = COLOR_SMALL_MAX;
-	for (int col = restFirst; col < nColors && col < MAX_COLORS; ++col) restRows += c.colorRows[col];
-	LAUNCH(w, k_color_fill, gC, 256, d, restFirst < MAX_COLORS ? restFirst : MAX_COLORS);
-	// (round 6: one single-workgroup launch sorts the hub group's segment of the row array in place - k_hub_build - where the
-	// last step's list was short enough for its keys to sit in LDS; the four launches below otherwise)
-	const bool hubBuildOne = hasHubs && !w->noHubBuild && w->last.nHubRows <= HUB_BUILD_LDS;
-	if (hubBuildOne)
-	{
-		LAUNCH(w, k_hub_build, 1, 1024, d, d.hubWide ? 1 : 0, (!w->noHubOrder && (d.hubWide || w->hubOrderAll)) ? 1 : 0, d.blockSort ? 1 : 0);
-		w->hubSteps += 1;
-	}
-	else if (hasHubs)
-	{
-		// the hub constraints in contact-index order (deterministic whatever the atomics of k_color_fill did)
-		LAUNCH(w, k_hub_flag, gridFor(d.capContacts), 256, d);
-		deviceExclusiveScan<int>(w->stream, d.keepFlag, d.keepScan, d.scanTmp, w->scanCtx, &d.st->c.nContacts, d.capContacts);
-		LAUNCH(w, k_hub_fill, gridFor(d.capContacts), 256, d);
-		// (the hub meets its partners in the order of their highest colour: b2d_kernels_solve_large.h, k_hub_order)
-		if (!w->noHubOrder && (d.hubWide || w->hubOrderAll)) LAUNCH(w, k_hub_order, 1, 1024, d, d.hubWide ? 0 : 1);
-		w->hubSteps += 1;
-	}
-	stampPhase(w, 7);
-	const int gK = gridFor(std::max(nLContacts / std::max(nColors, 1), 1) * 2);
-	// A colour launch is a chain of dependent loads per lane (~4.5 us whatever it holds): a lane that makes a second trip
-	// of the grid-stride loop pays the chain twice - the Tumbler's five biggest colours (41 000 - 42 000 rows against a grid
-	// of 39 000 lanes sized from the MEAN colour) took 8 us instead of 6. Sized per colour from this step's census now
-	// (+ what k_color_small may still add), in workgroups of 256 lanes so that the rows spread over all CUs.
-	const bool censusGrid = !exactLarge && nColors > 0 && nColors <= MAX_COLORS && !c.needRecolor && !s.censusVoid;
-	auto gridOfColor = [&](int col) -> int
-	{
-		if (!censusGrid || col < 0 || col >= MAX_COLORS) return gK;
-		return gridFor((size_t)c.colorRows[col] + 512, 256, 1 << 16);
-	};
-	const int gJ = gridFor(std::max(nLIslands, 1), 64, 1 << 16);
-	s.waitsBetweenWorkgroups = s.useBlocks || useSweep || (useSweepEnd && restFirst < nColors);
-	if (!safe && w->recoverOn && s.waitsBetweenWorkgroups) LAUNCH(w, k_solver_snapshot, gridFor(std::max(nLBodies, nLContacts)), 256, d, 0);
-	if (s.useBlocks)
-	{
-		// one resident grid for the whole sweep structure; colour boundaries are barriers inside the blocks, the cut rows
-		// hand-overs between them (b2d_kernels_solve_blocks.h)
-		if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 4; }
-		if ((rc = wipeHandoverRows(w))) return rc;
-		if (c.blkLanes == 512) LAUNCH(w, k_solve_blocks<512>, c.nBlocks, 512, d, sp, w->gridBar.p, w->dfEpoch);
-		else if (c.blkLanes == 256) LAUNCH(w, k_solve_blocks<256>, c.nBlocks, 256, d, sp, w->gridBar.p, w->dfEpoch);
-		else if (c.blkLanes == BLOCK_LANES) LAUNCH(w, k_solve_blocks<BLOCK_LANES>, c.nBlocks, BLOCK_LANES, d, sp, w->gridBar.p, w->dfEpoch);
-		else return setError(B2HIP_ERR_INVALID, "block partition made for an unknown workgroup size");
-		w->dfEpoch += 1;
-		w->blockSteps += 1;
-		w->blocksThisStep = true;
-		if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; }
-		if ((rc = launchDeferredSmallIslands(w, s))) return rc;
-	}
-	else
-	{
-	if ((rc = launchDeferredSmallIslands(w, s))) return rc;
-	TRACE("before_integrate");
-	if (w->debugTrace)
-	{
-		const size_t nb = w->bodies.size();
-		(void)w->dbgPreVel.ensure(nb, w->stream); (void)w->dbgVel.ensure(nb, w->stream); (void)w->dbgLi.ensure(nb + 64, w->stream);
-		HIP_TRY(hipMemcpyAsync(w->dbgPreVel.p, w->b_vel.p, nb * 16, hipMemcpyDeviceToDevice, w->stream));
-		HIP_TRY(hipMemcpyAsync(w->dbgLi.p, w->li_bodies.p, nb * 4, hipMemcpyDeviceToDevice, w->stream));
-		HIP_TRY(hipMemcpyAsync(w->dbgLi.p + nb, &w->d_state.p->c, 64 * 4 > sizeof(Counters) ? sizeof(Counters) : 64 * 4, hipMemcpyDeviceToDevice, w->stream));
-	}
-	// (timing mode 5: ONE event pair around the whole large-island solver family of the launch-per-colour path - integrate,
-	// constraint set-up, every sweep, impulses stored, positions, write-back and sleep)
-	if (w->kernelTiming == 5 && !safe) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 8; w->familyLaunchesAtStart = w->launchCount; }
-	const bool sortInIntegrate = hasJoints && !exactLarge && !w->debugTrace;
-	LAUNCH(w, k_large_integrate, gB, 256, d, sp, sortInIntegrate ? 1 : 0);
-	if (w->debugTrace) HIP_TRY(hipMemcpyAsync(w->dbgVel.p, w->b_vel.p, w->bodies.size() * 16, hipMemcpyDeviceToDevice, w->stream));
-	TRACE("integrate");
-	if (hasJoints && !exactLarge && !sortInIntegrate) LAUNCH(w, k_joints_sort, gJ, 64, d);
-	// (the warm start body by body in one launch - k_large_warm - where the sweep would be a launch per colour: k_large_init
-	// leaves the deltas for it)
-	const bool bodyWarm = w->bodyWarm && w->sweepEnd && !exactLarge && !w->debugTrace && !useSweep && sp.warmStarting && nColors <= MAX_COLORS;
-	LAUNCH(w, k_large_init, gC, 256, d, sp, bodyWarm ? 1 : 0);
-	TRACE("init");
-	// colours that own no constraint (the partition keeps two colour ranges apart) are not launched
-	const uint64_t colorMask = exactLarge ? ~0ull : ((uint64_t)w->h_dstate->c.colorMaskLo | ((uint64_t)w->h_dstate->c.colorMaskHi << 32));
-	auto colorUsed = [&](int col) { return col >= 64 || ((colorMask >> col) & 1ull) != 0; };
-	// every launch of k_blocks_sweep tags its hand-over rows with an epoch of its own
-	auto sweep = [&](int mode) -> int
-	{
-		if (int rcw = wipeHandoverRows(w)) return rcw;
-		if (c.blkLanes == 512) LAUNCH(w, k_blocks_sweep<512>, c.nBlocks, 512, d, sp, mode, w->gridBar.p, w->dfEpoch);
-		else if (c.blkLanes == 256) LAUNCH(w, k_blocks_sweep<256>, c.nBlocks, 256, d, sp, mode, w->gridBar.p, w->dfEpoch);
-		else if (c.blkLanes == BLOCK_LANES) LAUNCH(w, k_blocks_sweep<BLOCK_LANES>, c.nBlocks, BLOCK_LANES, d, sp, mode, w->gridBar.p, w->dfEpoch);
-		else return setError(B2HIP_ERR_INVALID, "block partition made for an unknown workgroup size");
+		if (int rc = wipeHandoverRows(w)) return rc;
+		if (int rc = launch()) return rc;
 		w->dfEpoch += 1;
 		return 0;
-	};
+	}
+
+	// k_blocks_sweep in `mode` (0 warm start, 1 velocity, 2 position) over the blocks of the partition; WHOLE_SOLVE: k_solve_blocks,
+	// the whole sweep structure in one resident grid. (The compiler emits the instantiations in the order the dispatches name
+	// them first - here k_solve_blocks<512, 256, 1024>, then k_blocks_sweep's: a reordered ladder moves kernels in the code object.)
+	static const int WHOLE_SOLVE = -1;
+	int launchBlocks(int mode)
+	{
+		const Counters& c = s.c;
+		return withEpoch([&]() -> int
+		{
+			if (mode == WHOLE_SOLVE && c.blkLanes == 512) LAUNCH(w, k_solve_blocks<512>, c.nBlocks, 512, d, sp, w->gridBar.p, w->dfEpoch);
+			else if (mode == WHOLE_SOLVE && c.blkLanes == 256) LAUNCH(w, k_solve_blocks<256>, c.nBlocks, 256, d, sp, w->gridBar.p, w->dfEpoch);
+			else if (mode == WHOLE_SOLVE && c.blkLanes == BLOCK_LANES) LAUNCH(w, k_solve_blocks<BLOCK_LANES>, c.nBlocks, BLOCK_LANES, d, sp, w->gridBar.p, w->dfEpoch);
+			else if (mode != WHOLE_SOLVE && c.blkLanes == 512) LAUNCH(w, k_blocks_sweep<512>, c.nBlocks, 512, d, sp, mode, w->gridBar.p, w->dfEpoch);
+			else if (mode != WHOLE_SOLVE && c.blkLanes == 256) LAUNCH(w, k_blocks_sweep<256>, c.nBlocks, 256, d, sp, mode, w->gridBar.p, w->dfEpoch);
+			else if (mode != WHOLE_SOLVE && c.blkLanes == BLOCK_LANES) LAUNCH(w, k_blocks_sweep<BLOCK_LANES>, c.nBlocks, BLOCK_LANES, d, sp, mode, w->gridBar.p, w->dfEpoch);
+			else return setError(B2HIP_ERR_INVALID, "block partition made for an unknown workgroup size");
+			return 0;
+		});
+	}
+
 	// the hub sweeps: eight waves that fetch their chunks of hub constraints ahead of their turn (one wave on request)
-	auto hubSweepLaunch = [&](int mode, int useGuess, int behindWide = 0) -> int
+	int launchHub(int mode, int useGuess, int behindWide)
 	{
 		if (w->hubWaves == 1) LAUNCH(w, k_large_hub<1>, 1, 64, d, mode, useGuess, behindWide);
 		else LAUNCH(w, k_large_hub<8>, 1, 512, d, mode, useGuess, behindWide);
 		return 0;
-	};
-	if (useSweep) w->sweepSteps += 1;
-	// ---- the end of every sweep in ONE single-workgroup launch (b2d_kernels_sweep_end.h): the tail colours - those this
-	// step's colour census (k_color_check, published with the island census) found small, from the highest colour down -
-	// the hub rows, the joint walk, the verdict of a position iteration. Which colours are "tail" changes nothing in the
-	// result (k_sweep_end does k_large_velocity's / k_large_position's arithmetic row for row): a pure launch-count matter.
-	const bool useRest = useSweepEnd && restFirst < nColors;
-	int tailFirst = useRest ? restFirst : nColors;
-	if (useSweepEnd && w->sweepTail && !useRest && !useSweep && !c.needRecolor && !s.censusVoid && nColors <= MAX_COLORS)
-	{
-		long long sum = 0;
-		while (tailFirst > 0 && c.colorRows[tailFirst - 1] <= w->tailRowsMax && sum + c.colorRows[tailFirst - 1] <= 8ll * w->tailRowsMax)
-		{
-			sum += c.colorRows[tailFirst - 1];
-			tailFirst -= 1;
-		}
 	}
-	bool tailAny = false;
-	for (int col = tailFirst; col < nColors && !useRest; ++col) tailAny = tailAny || colorUsed(col);
-	// (every launch of k_large_rest tags its hand-over rows with an epoch of its own, like k_blocks_sweep)
-	auto restLaunch = [&](int mode) -> int
+
+	// The rest colours of one sweep as data flow per body.
+	int launchRest(int mode)
 	{
-		if (!useRest) return 0;
-		if (int rcw = wipeHandoverRows(w)) return rcw;
-		int gR = (int)((restRows + 255) / 256);
+		int gR = (int)((p.restRows + 255) / 256);
 		// (the workgroups wait for one another: no more of them than are resident together - the rest walk in strides)
 		if (w->restMaxWG > 0) gR = std::min(gR, w->restMaxWG);
-		if (mode == 0) LAUNCH(w, k_large_rest<0>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
-		else if (mode == 1) LAUNCH(w, k_large_rest<1>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
-		else LAUNCH(w, k_large_rest<2>, gR, 256, d, restFirst, nColors, w->gridBar.p, w->dfEpoch);
-		w->dfEpoch += 1;
-		return 0;
-	};
-	w->lastTailFirst = tailFirst;
-	w->lastSweepLaunches = 0;
-	const int bigEnd = useSweep ? 0 : tailFirst; // colours [0, bigEnd) are launches of their own
-	// The hub rows the one fixed point cannot take are swept lane after lane inside k_sweep_end - a handful on the Tumbler
-	// (boxes in the corners). An island that kept many of them in the LAST step (several hubs, constraints swept in order for
-	// lack of a home block; the census still carries that step's counts) gets k_large_hub's eight prefetching waves for
-	// them: k_sweep_end up to the fixed point, k_large_hub, k_sweep_end for what follows the hub rows. (Either way a valid
-	// sweep; which one is decided from counters a snapshot carries, so a loaded world decides alike.)
-	const bool leftoverApart = useSweepEnd && hasHubs && d.hubWide && c.nHubRows - c.nHubWide > SE_LEFT_INLINE_MAX;
-	auto sweepEndOne = [&](int mode, int tf, int te, int what) -> int
+		return withEpoch([&]() -> int
+		{
+			if (mode == 0) LAUNCH(w, k_large_rest<0>, gR, 256, d, p.restFirst, s.nColors, w->gridBar.p, w->dfEpoch);
+			else if (mode == 1) LAUNCH(w, k_large_rest<1>, gR, 256, d, p.restFirst, s.nColors, w->gridBar.p, w->dfEpoch);
+			else LAUNCH(w, k_large_rest<2>, gR, 256, d, p.restFirst, s.nColors, w->gridBar.p, w->dfEpoch);
+			return 0;
+		});
+	}
+
+	// Tail colours [tf, te) and what follows them (`what`: SE_*), in one workgroup.
+	int launchSweepEnd(int mode, int tf, int te, int what)
 	{
 		if (mode == 0) LAUNCH(w, k_sweep_end<0>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
 		else if (mode == 1) LAUNCH(w, k_sweep_end<1>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
 		else LAUNCH(w, k_sweep_end<2>, 1, SWEEP_END_LANES, d, sp, tf, te, what, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
-		w->lastSweepLaunches += 1;
 		return 0;
-	};
-	// ---- k_large_rest and k_sweep_end of one sweep as ONE launch (k_rest_hub, round 6): the rest rows in gF workgroups of
-	// 512 lanes, the hub rows / joints / verdict in one more that waits for what it needs of them as tagged rows. All
-	// workgroups must be resident together (restHubMaxWG: the occupancy query at world creation).
-	const bool fuseHub = useRest && w->restHub && (hasHubs || hasJoints) && !leftoverApart && w->restHubMaxWG > 1;
-	auto restHubLaunch = [&](int mode, int what) -> int
+	}
+
+	// The rest colours and the end of the sweep in one launch (velocity and position sweeps only).
+	int launchRestHub(int mode, int what)
 	{
-		if (int rcw = wipeHandoverRows(w)) return rcw;
 		// (a grid that does not hold every row walks them in strides)
-		int gF = (int)((restRows + SWEEP_END_LANES - 1) / SWEEP_END_LANES);
+		int gF = (int)((p.restRows + SWEEP_END_LANES - 1) / SWEEP_END_LANES);
 		gF = std::max(1, std::min(gF, w->restHubMaxWG - 1));
-		if (mode == 2) w->restArrived += gF; // (the verdict of a position iteration waits for them: bar[5])
-		if (mode == 1) LAUNCH(w, k_rest_hub<1>, gF + 1, SWEEP_END_LANES, d, sp, restFirst, nColors, what, w->gridBar.p, w->dfEpoch, w->restArrived, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
-		else LAUNCH(w, k_rest_hub<2>, gF + 1, SWEEP_END_LANES, d, sp, restFirst, nColors, what, w->gridBar.p, w->dfEpoch, w->restArrived, (int*)nullptr);
-		w->dfEpoch += 1;
-		w->lastSweepLaunches += 1;
-		return 0;
-	};
-	bool noTail = false;
-	auto sweepEndLaunch = [&](int mode, int what) -> int
-	{
-		if (!what && (!tailAny || noTail)) return 0;
-		const int tf = (useSweep || useRest || noTail) ? 0 : tailFirst, te = (useSweep || useRest || noTail) ? 0 : nColors;
-		if (leftoverApart && (what & SE_HUB))
+		return withEpoch([&]() -> int
 		{
-			int rcl = sweepEndOne(mode, tf, te, (what & (SE_HUB | SE_GUESS)) | SE_HUB_WIDE_ONLY);
-			if (rcl) return rcl;
-			rcl = hubSweepLaunch(mode, (what & SE_GUESS) ? 1 : 0, 1);
-			if (rcl) return rcl;
-			const int rest = what & ~(SE_HUB | SE_GUESS);
-			return rest ? sweepEndOne(mode, 0, 0, rest) : 0;
-		}
-		return sweepEndOne(mode, tf, te, what);
-	};
-	if (sp.warmStarting)
+			if (mode == 2) w->restArrived += gF; // (the verdict of a position iteration waits for them: bar[5])
+			if (mode == 1) LAUNCH(w, k_rest_hub<1>, gF + 1, SWEEP_END_LANES, d, sp, p.restFirst, s.nColors, what, w->gridBar.p, w->dfEpoch, w->restArrived, w->sweepStamps ? w->gridBar.p : (int*)nullptr);
+			else LAUNCH(w, k_rest_hub<2>, gF + 1, SWEEP_END_LANES, d, sp, p.restFirst, s.nColors, what, w->gridBar.p, w->dfEpoch, w->restArrived, (int*)nullptr);
+			return 0;
+		});
+	}
+
+	// The rows of the large islands by colour (unless the block solvers sort their own), rest colours noted on their bodies,
+	// the hub group's rows listed in order.
+	int layoutRows()
 	{
-		if (useSweep) { rc = sweep(0); if (rc) return rc; }
-		else if (bodyWarm) LAUNCH(w, k_large_warm, gB, 256, d);
+		if (!d.blockSort) LAUNCH(w, k_color_scan, 1, 64, d); // (segments by colour: the block solvers sort their rows themselves)
+		LAUNCH(w, k_color_fill, p.gC, 256, d, p.restFirst < MAX_COLORS ? p.restFirst : MAX_COLORS);
+		if (!s.hasHubs) return 0;
+		const int order = (!w->noHubOrder && (d.hubWide || w->hubOrderAll)) ? 1 : 0;
+		if (p.hubBuildOne) LAUNCH(w, k_hub_build, 1, 1024, d, d.hubWide ? 1 : 0, order, d.blockSort ? 1 : 0);
 		else
 		{
-			for (int col = 0; col < bigEnd; ++col)
-				if (colorUsed(col)) LAUNCH(w, k_large_velocity, gridOfColor(col), 256, d, col, 0);
-			rc = restLaunch(0);
-			if (rc) return rc;
+			// the hub constraints in contact-index order (deterministic whatever the atomics of k_color_fill did)
+			LAUNCH(w, k_hub_flag, gridFor(d.capContacts), 256, d);
+			deviceExclusiveScan<int>(w->stream, d.keepFlag, d.keepScan, d.scanTmp, w->scanCtx, &d.st->c.nContacts, d.capContacts);
+			LAUNCH(w, k_hub_fill, gridFor(d.capContacts), 256, d);
+			// (the hub meets its partners in the order of their highest colour: b2d_kernels_solve_large.h, k_hub_order)
+			if (order) LAUNCH(w, k_hub_order, 1, 1024, d, d.hubWide ? 0 : 1);
 		}
-		if (useSweepEnd)
-		{
-			// (b2Island.cpp:256-268: the joints' InitVelocityConstraints follows the contacts' warm start; the first velocity
-			// iteration then begins with the joints)
-			const int what0 = (hasHubs ? SE_HUB : 0) | (hasJoints ? SE_JOINTS_INIT | (sp.velIters > 0 ? SE_JOINTS_VEL : 0) : 0);
-			noTail = bodyWarm; // (after k_large_warm every colour has had its warm start: only what follows the colours is left)
-			rc = sweepEndLaunch(0, what0);
-			noTail = false;
-			if (rc) return rc;
-		}
-		else if (hasHubs) { rc = hubSweepLaunch(0, 0); if (rc) return rc; }
+		w->hubSteps += 1;
+		return 0;
 	}
-	TRACE("warmstart");
-	if (hasJoints && !(useSweepEnd && sp.warmStarting)) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 0);
-	for (int it = 0; it < sp.velIters; ++it)
+
+	// one resident grid for the whole sweep structure; colour boundaries are barriers inside the blocks, the cut rows
+	// hand-overs between them (b2d_kernels_solve_blocks.h)
+	int solveResident()
+	{
+		int rc = 0;
+		if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 4; }
+		if ((rc = launchBlocks(WHOLE_SOLVE))) return rc;
+		w->blockSteps += 1;
+		w->blocksThisStep = true;
+		if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; }
+		return launchDeferredSmallIslands(w, s);
+	}
+
+	// b2Island.cpp:193-254: velocities integrated, joints in their order, the constraints of the contacts set up.
+	int setUp()
+	{
+		TRACE("before_integrate");
+		if (w->debugTrace)
+		{
+			const size_t nb = w->bodies.size();
+			(void)w->dbgPreVel.ensure(nb, w->stream); (void)w->dbgVel.ensure(nb, w->stream); (void)w->dbgLi.ensure(nb + 64, w->stream);
+			HIP_TRY(hipMemcpyAsync(w->dbgPreVel.p, w->b_vel.p, nb * 16, hipMemcpyDeviceToDevice, w->stream));
+			HIP_TRY(hipMemcpyAsync(w->dbgLi.p, w->li_bodies.p, nb * 4, hipMemcpyDeviceToDevice, w->stream));
+			HIP_TRY(hipMemcpyAsync(w->dbgLi.p + nb, &w->d_state.p->c, 64 * 4 > sizeof(Counters) ? sizeof(Counters) : 64 * 4, hipMemcpyDeviceToDevice, w->stream));
+		}
+		// (timing mode 5: ONE event pair around the whole large-island solver family of the launch-per-colour path - integrate,
+		// constraint set-up, every sweep, impulses stored, positions, write-back and sleep)
+		if (w->kernelTiming == 5 && !p.safe) { int rc = ktRecord(w); if (rc) return rc; w->ktKind = 8; w->familyLaunchesAtStart = w->launchCount; }
+		LAUNCH(w, k_large_integrate, p.gB, 256, d, sp, p.sortInIntegrate ? 1 : 0);
+		if (w->debugTrace) HIP_TRY(hipMemcpyAsync(w->dbgVel.p, w->b_vel.p, w->bodies.size() * 16, hipMemcpyDeviceToDevice, w->stream));
+		TRACE("integrate");
+		if (s.hasJoints && !s.exactLarge && !p.sortInIntegrate) LAUNCH(w, k_joints_sort, p.gJ, 64, d);
+		LAUNCH(w, k_large_init, p.gC, 256, d, sp, p.bodyWarm ? 1 : 0);
+		TRACE("init");
+		return 0;
+	}
+
+	// The colours of one sweep that are launches (mode 0 warm start, 1 velocity iteration `it`, 2 position iteration `it`):
+	// ONE launch of k_blocks_sweep over the blocks, else a launch per colour in [0, bigEnd).
+	int sweepColours(int mode, int it)
+	{
+		if (s.useSweep) return launchBlocks(mode);
+		const bool timeIt = mode == 1 && w->kernelTiming == 1;
+		for (int col = 0; col < p.bigEnd; ++col)
+		{
+			if (!colorUsed(p, col)) continue;
+			if (timeIt) { int rc = ktRecord(w); if (rc) return rc; w->ktKind = 1; }
+			if (mode == 2) LAUNCH(w, k_large_position, gridOfColor(s, p, col), 256, d, col);
+			else LAUNCH(w, k_large_velocity, gridOfColor(s, p, col), 256, d, col, mode);
+			if (timeIt) { int rc = ktRecord(w); if (rc) return rc; }
+			if (mode > 0 && w->debugTrace) TRACE(((mode == 1 ? "vel" : "pos") + std::to_string(it) + "_c" + std::to_string(col)).c_str());
+		}
+		return 0;
+	}
+
+	// What follows the colours in the sweep of (mode, it), as k_sweep_end's / k_rest_hub's `what` word.
+	int whatFollows(int mode, int it) const
+	{
+		int what = s.hasHubs ? SE_HUB | (it > 0 ? SE_GUESS : 0) : 0;
+		// (b2Island.cpp:256-268: the joints' InitVelocityConstraints follows the contacts' warm start; the first velocity
+		// iteration then begins with the joints. The joint walk of an iteration is the last act of the sweep before it)
+		if (mode == 0 && s.hasJoints) what |= SE_JOINTS_INIT | (sp.velIters > 0 ? SE_JOINTS_VEL : 0);
+		if (mode == 1 && s.hasJoints && it + 1 < sp.velIters) what |= SE_JOINTS_VEL;
+		if (mode == 2) what |= (s.hasJoints ? SE_JOINTS_POS : 0) | SE_POS_END | (it + 1 < sp.posIters ? SE_POS_BEGIN : 0);
+		return what;
+	}
+
+	// The end of the sweep of (mode, it), behind its launched colours: the rest colours, the tail colours, the hub rows, the
+	// joint walk, the verdict of a position iteration. The warm start (mode 0, it 0) never fuses, a position sweep only with
+	// restHub > 1. `coloursDone`: every colour has had its sweep (after k_large_warm) - only what follows the colours is left.
+	int endOfSweep(int mode, int it, bool coloursDone = false)
+	{
+		const int what = whatFollows(mode, it);
+		if (p.fuseHub && (mode == 1 || (mode == 2 && w->restHub > 1))) return launchRestHub(mode, what);
+		if (p.useRest && !coloursDone)
+			if (int rc = launchRest(mode)) return rc;
+		if (!p.useSweepEnd)
+		{
+			if (s.hasHubs)
+				if (int rc = launchHub(mode, it > 0 ? 1 : 0, 0)) return rc;
+			if (mode == 2 && s.hasJoints) LAUNCH(w, k_large_joints, p.gJ, 64, d, sp, 2);
+			if (mode == 2) LAUNCH(w, k_large_pos_end, 1, 256, d);
+			return 0;
+		}
+		const bool tail = !(s.useSweep || p.useRest || coloursDone);
+		if (!what && !(tail && p.tailAny)) return 0;
+		const int tf = tail ? p.tailFirst : 0, te = tail ? s.nColors : 0;
+		if (!(p.leftoverApart && (what & SE_HUB))) return launchSweepEnd(mode, tf, te, what);
+		// (leftover hub rows apart: up to the fixed point, k_large_hub behind it, then what follows the hub rows)
+		if (int rc = launchSweepEnd(mode, tf, te, (what & (SE_HUB | SE_GUESS)) | SE_HUB_WIDE_ONLY)) return rc;
+		if (int rc = launchHub(mode, (what & SE_GUESS) ? 1 : 0, 1)) return rc;
+		const int behind = what & ~(SE_HUB | SE_GUESS);
+		return behind ? launchSweepEnd(mode, 0, 0, behind) : 0;
+	}
+
+	int warmStart()
+	{
+		if (sp.warmStarting)
+		{
+			if (p.bodyWarm) LAUNCH(w, k_large_warm, p.gB, 256, d);
+			else if (int rc = sweepColours(0, 0)) return rc;
+			if (int rc = endOfSweep(0, 0, p.bodyWarm)) return rc;
+		}
+		TRACE("warmstart");
+		if (s.hasJoints && !(p.useSweepEnd && sp.warmStarting)) LAUNCH(w, k_large_joints, p.gJ, 64, d, sp, 0);
+		return 0;
+	}
+
+	int velocityIteration(int it)
 	{
 		// (with k_sweep_end the joint walk of iteration it is the last act of the sweep before it)
-		if (hasJoints && !(useSweepEnd && (it > 0 || sp.warmStarting))) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 1);
-		if (useSweep) { rc = sweep(1); if (rc) return rc; }
-		else
-		for (int col = 0; col < bigEnd; ++col)
-		{
-			if (!colorUsed(col)) continue;
-			if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; w->ktKind = 1; }
-			LAUNCH(w, k_large_velocity, gridOfColor(col), 256, d, col, 1);
-			if (w->kernelTiming == 1) { rc = ktRecord(w); if (rc) return rc; }
-			if (w->debugTrace) TRACE(("vel" + std::to_string(it) + "_c" + std::to_string(col)).c_str());
-		}
-		const int what1 = (hasHubs ? SE_HUB | (it > 0 ? SE_GUESS : 0) : 0) | (hasJoints && it + 1 < sp.velIters ? SE_JOINTS_VEL : 0);
-		if (fuseHub && !useSweep) { rc = restHubLaunch(1, what1); if (rc) return rc; }
-		else
-		{
-			if (!useSweep) { rc = restLaunch(1); if (rc) return rc; }
-			if (useSweepEnd)
-			{
-				rc = sweepEndLaunch(1, what1);
-				if (rc) return rc;
-			}
-			else if (hasHubs) { rc = hubSweepLaunch(1, it > 0 ? 1 : 0); if (rc) return rc; }
-		}
+		if (s.hasJoints && !(p.useSweepEnd && (it > 0 || sp.warmStarting))) LAUNCH(w, k_large_joints, p.gJ, 64, d, sp, 1);
+		if (int rc = sweepColours(1, it)) return rc;
+		return endOfSweep(1, it);
 	}
-	// (one launch for the three: k_large_after_velocity; apart where a trace wants to see each)
-	const bool afterFused = !w->debugTrace && sp.posIters > 0;
-	if (afterFused) LAUNCH(w, k_large_after_velocity, gridFor(std::max(nLContacts, nLBodies)), 256, d, sp);
-	else
+
+	// b2Island.cpp:280-297: impulses stored, positions integrated (and the first position iteration begun).
+	int afterVelocity()
 	{
-		LAUNCH(w, k_large_store_impulses, gC, 256, d);
-		TRACE("store_impulses");
-		LAUNCH(w, k_large_integrate_positions, gB, 256, d, sp);
-		TRACE("integrate_positions");
+		if (p.afterFused) LAUNCH(w, k_large_after_velocity, gridFor(std::max(s.nLContacts, s.nLBodies)), 256, d, sp);
+		else
+		{
+			LAUNCH(w, k_large_store_impulses, p.gC, 256, d);
+			TRACE("store_impulses");
+			LAUNCH(w, k_large_integrate_positions, p.gB, 256, d, sp);
+			TRACE("integrate_positions");
+		}
+		return 0;
 	}
-	for (int it = 0; it < sp.posIters; ++it)
+
+	int positionIteration(int it)
 	{
-		if ((!useSweepEnd || it == 0) && !(afterFused && it == 0)) LAUNCH(w, k_large_pos_begin, gridFor(nLIslands), 256, d);
-		if (useSweep) { rc = sweep(2); if (rc) return rc; }
-		else
-		for (int col = 0; col < bigEnd; ++col)
-		{
-			if (!colorUsed(col)) continue;
-			LAUNCH(w, k_large_position, gridOfColor(col), 256, d, col);
-			if (w->debugTrace) TRACE(("pos" + std::to_string(it) + "_c" + std::to_string(col)).c_str());
-		}
-		const int what2 = (hasHubs ? SE_HUB | (it > 0 ? SE_GUESS : 0) : 0) | (hasJoints ? SE_JOINTS_POS : 0) | SE_POS_END | (it + 1 < sp.posIters ? SE_POS_BEGIN : 0);
-		if (fuseHub && !useSweep && w->restHub > 1) { rc = restHubLaunch(2, what2); if (rc) return rc; continue; }
-		if (!useSweep) { rc = restLaunch(2); if (rc) return rc; }
-		if (useSweepEnd)
-		{
-			rc = sweepEndLaunch(2, what2);
-			if (rc) return rc;
-		}
+		// (k_sweep_end begins the next iteration itself, k_large_after_velocity the first)
+		if ((!p.useSweepEnd || it == 0) && !(p.afterFused && it == 0)) LAUNCH(w, k_large_pos_begin, gridFor(s.nLIslands), 256, d);
+		if (int rc = sweepColours(2, it)) return rc;
+		return endOfSweep(2, it);
+	}
+
+	int run()
+	{
+		int rc = layoutRows();
+		if (rc) return rc;
+		stampPhase(w, 7);
+		if (!p.safe && w->recoverOn && p.waitsBetweenWorkgroups) LAUNCH(w, k_solver_snapshot, gridFor(std::max(s.nLBodies, s.nLContacts)), 256, d, 0);
+		if (s.useBlocks) rc = solveResident();
 		else
 		{
-			if (hasHubs) { rc = hubSweepLaunch(2, it > 0 ? 1 : 0); if (rc) return rc; }
-			if (hasJoints) LAUNCH(w, k_large_joints, gJ, 64, d, sp, 2);
-			LAUNCH(w, k_large_pos_end, 1, 256, d);
+			// b2Island::Solve sweep by sweep: k_blocks_sweep or a launch per colour
+			rc = launchDeferredSmallIslands(w, s);
+			if (rc == 0) rc = setUp();
+			if (rc == 0 && s.useSweep) w->sweepSteps += 1;
+			if (rc == 0) rc = warmStart();
+			for (int it = 0; rc == 0 && it < sp.velIters; ++it) rc = velocityIteration(it);
+			if (rc == 0) rc = afterVelocity();
+			for (int it = 0; rc == 0 && it < sp.posIters; ++it) rc = positionIteration(it);
 		}
+		if (rc) return rc;
+		LAUNCH(w, k_large_finalize, p.gB, 256, d, sp);
+		TRACE("finalize");
+		LAUNCH(w, k_large_sleep, p.gB, 256, d, sp);
+		return 0;
 	}
-	}
-	LAUNCH(w, k_large_finalize, gB, 256, d, sp);
-	TRACE("finalize");
-	LAUNCH(w, k_large_sleep, gB, 256, d, sp);
-	return 0;
-}
+};
 
 // Did every wait between workgroups come to its end? (the overflow word, published by one lane behind the solver; polled)
 // If not - or if k_solve_blocks ran on an incomplete colouring - the saved state goes back and the large islands are
@@ -1131,7 +1206,7 @@ static int recoverLarge(b2hip_world* w, SolveStep& s)
 		if (w->traceRecovery) fprintf(stderr, "[b2hip] the resident solver ran on an incomplete colouring (overflow 0x%x, %d without a colour): colouring finished, the solve once more\n", flags, w->h_solverWord[2]);
 		// finish the colouring first: the grid-wide rounds over what k_color_small left open
 		if (int rc = colorRoundsUntilDone(w, s, w->h_dstate->c.nUncolored, 8)) return rc;
-		if (w->h_dstate->c.overflow & 4) s.colorSpill = true;
+		if (w->h_dstate->c.overflow & 4) s.colorSpill = s.hasHubs = true;
 		s.censusVoid = true;
 		w->colorRecoveries += 1;
 	}
@@ -1139,7 +1214,11 @@ static int recoverLarge(b2hip_world* w, SolveStep& s)
 	s.c.nColors = s.nColors;
 	memcpy(s.c.colorRows, w->h_dstate->c.colorRows, sizeof(s.c.colorRows));
 	if (flags & 64) w->solverRecoveries += 1;
-	return solveLargePass(w, s, true);
+	// the solver choice of the second pass: rows by colour, a launch per colour
+	s.useBlocks = s.useSweep = false;
+	s.colorsOnDevice = false;
+	d.blockSort = 0;
+	return LargePass(w, s, true).run();
 }
 
 static int solveLargeIslands(b2hip_world* w, SolveStep& s)
@@ -1151,13 +1230,14 @@ static int solveLargeIslands(b2hip_world* w, SolveStep& s)
 	if (s.colorSpill) w->colorRecoveries += 1;
 	// (a constraint without a colour carries HUB_COLOR: the colours to launch end below it)
 	if (!s.exactLarge && s.nColors > HUB_COLOR) s.nColors = HUB_COLOR;
-	if (int rc = solveLargePass(w, s, false)) return rc;
+	LargePass pass(w, s, false);
+	if (int rc = pass.run()) return rc;
 	if (w->kernelTiming == 5 && w->ktKind == 8)
 	{
 		w->familyLaunches = (int)(w->launchCount - w->familyLaunchesAtStart);
 		if (int rc = ktRecord(w)) return rc;
 	}
-	if (w->recoverOn && s.waitsBetweenWorkgroups)
+	if (w->recoverOn && pass.p.waitsBetweenWorkgroups)
 		if (int rc = recoverLarge(w, s)) return rc;
 	TRACE("sleep");
 	if (s.sideStream) HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0));

@@ -2,7 +2,7 @@
 (Box2D/Dynamics/b2World.cpp:1613-1710); the device's fast paths have places where a step could fail - a wait between the
 workgroups of a resident / data-flow solver kernel that times out (a co-tenant on the device, a workgroup that was not
 resident), a constraint that finds no colour free on its two bodies, incremental colouring rounds that do not converge. Each
-used to end the step with an error and leave a world that refuses to step. Now (box2d-mt_amd/csrc/b2hip_host_phases.h: runLarge):
+used to end the step with an error and leave a world that refuses to step. Now (box2d-mt_amd/csrc/b2hip_host_phases.h: LargePass, recoverLarge):
 
   * a timed-out wait: the state the solver had changed is put back (k_solver_snapshot) and the solve runs once more on the
     plain path - rows by colour, a launch per colour, hub rows and tail colours in ONE workgroup: nothing waits for another

@@ -23,12 +23,13 @@ import b2harness as bh
 pytestmark = pytest.mark.gpu
 
 KEYS = ("B2HIP_HUB_SERIAL", "B2HIP_NO_SWEEP_END", "B2HIP_NO_TAIL", "B2HIP_HUB_WIDE", "B2HIP_TAIL_ROWS", "B2HIP_SOLVER_LAUNCHES",
-        "B2HIP_NO_REST", "B2HIP_REST_ROWS", "B2HIP_FORCE_LARGE", "B2HIP_HUB_WAVES", "B2HIP_NO_BODY_WARM", "B2HIP_REST_HUB", "B2HIP_HUB_ORDER", "B2HIP_NO_HUB_ORDER", "B2HIP_NO_HUB_BUILD")
+        "B2HIP_NO_REST", "B2HIP_REST_ROWS", "B2HIP_FORCE_LARGE", "B2HIP_HUB_WAVES", "B2HIP_NO_BODY_WARM", "B2HIP_REST_HUB", "B2HIP_HUB_ORDER", "B2HIP_NO_HUB_ORDER", "B2HIP_NO_HUB_BUILD",
+        "B2HIP_TRACE")
 CCD = bh.F_SLEEP | bh.F_WARM | bh.F_CONTINUOUS
 LAUNCHES = {"B2HIP_SOLVER_LAUNCHES": "1"}  # no resident block solver, no k_blocks_sweep: a launch per colour
 
 
-def run(amd, monkeypatch, scene, steps, env, **kw):
+def run(amd, monkeypatch, scene, steps, env, after=None, **kw):
     for k in KEYS:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
@@ -39,6 +40,8 @@ def run(amd, monkeypatch, scene, steps, env, **kw):
         w.step(1)
         out.append((bh.fnv1a64(w.bodies()), w.contact_count))
     b = w.bodies()
+    if after is not None:
+        after(w)  # (a look at the world behind its last step)
     w.close()
     for k in KEYS:
         monkeypatch.delenv(k, raising=False)
@@ -77,6 +80,43 @@ def test_sweep_end_folding_is_bit_identical_to_the_launches_it_replaces(amd, mon
         other, _ = run(amd, monkeypatch, scene, steps, dict(serial, **env), **kw)
         first = first_diff(base, other)
         assert first is None, "%s, %s: differs from the launch sequence of round 4 at step %d" % (name, label, first)
+
+
+def stage_labels(w):
+    """The labels of the last step's B2HIP_TRACE record (b2hip_debug_trace), in order."""
+    import ctypes as C
+    import b2hip
+    L = b2hip.lib()
+    L.b2hip_debug_trace.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
+    L.b2hip_debug_trace.restype = C.c_int
+    out, label, h = [], C.create_string_buffer(64), C.c_uint64(0)
+    while L.b2hip_debug_trace(w.device_world(), len(out), label, 64, C.byref(h)) == 0:
+        out.append(label.value.decode())
+    return out
+
+
+TRACED = [("pyramid40, CCD (no hub, no joint)", bh.PYRAMID, 60, dict(p0=40, p1=1, flags=CCD)),
+          ("tumbler60 (hub + motor joint)", bh.TUMBLER, 120, dict(p0=60)),
+          ("machines buried (joints)", bh.MACHINES, 160, dict(p0=600, p1=6, seed=3))]
+
+
+@pytest.mark.parametrize("case", TRACED, ids=[c[0] for c in TRACED])
+def test_traced_solve_is_bit_identical_to_the_launch_per_colour_solve(amd, monkeypatch, case):
+    """B2HIP_TRACE=1 takes the launches apart that a plain step fuses (k_large_store_impulses + k_large_integrate_positions for
+    k_large_after_velocity, k_joints_sort apart from k_large_integrate, k_large_pos_begin on its own) and copies state between
+    them: the same arithmetic, so the same bits. B2HIP_NO_SWEEP_END on both sides: the trace alone would leave the hub rows as
+    one fixed point, in another order - what is compared is the unfused launches, not an order."""
+    name, scene, steps, kw = case
+    labels = []
+    base, _ = run(amd, monkeypatch, scene, steps, dict(LAUNCHES, B2HIP_NO_SWEEP_END="1"), **kw)
+    traced, _ = run(amd, monkeypatch, scene, steps, {"B2HIP_TRACE": "1", "B2HIP_NO_SWEEP_END": "1"}, after=lambda w: labels.extend(stage_labels(w)), **kw)
+    first = first_diff(base, traced)
+    assert first is None, "%s: the traced solve differs from the launch-per-colour solve at step %d" % (name, first)
+    if scene == bh.TUMBLER:
+        assert labels, "no trace was recorded"
+        assert labels[:4] == ["before_integrate", "integrate", "init", "warmstart"], labels[:4]
+        assert labels.index("store_impulses") < labels.index("integrate_positions"), labels
+        assert labels[-2:] == ["finalize", "sleep"], labels[-2:]
 
 
 def test_hub_rows_as_one_fixed_point_agree_with_the_lane_after_lane_sweep(amd, monkeypatch):
