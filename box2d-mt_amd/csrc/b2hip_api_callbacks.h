@@ -188,6 +188,8 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 //     kept the set, [1 .. 6] rebuilds because the set was invalid / stale / built under another mask / too full / the world
 //     is sharded / B2HIP_KEYSET_KEEP=0, [7] tombstones written, [8] keys inserted into a kept set, [9] deletes that found no
 //     key, [10] slots in use now (live + tombstones), [11] the mask now.
+// 24: one long long: narrow phases since the world was created in which k_collide<0, false, true> stored the compacted contact
+//     array itself (no scan of the keep flags, no k_compact_contacts behind it).
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -244,6 +246,12 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 		stats[KS_STATS] = c.ksFill;
 		stats[KS_STATS + 1] = c.ksMask;
 		memcpy(out, stats + first, (size_t)count * sizeof(long long));
+		return 0;
+	}
+	case 24:
+	{
+		if (first != 0 || count != 1) return setError(B2HIP_ERR_INVALID, "narrow-phase statistics: [0, 1)");
+		memcpy(out, &w->statCollideCompact, sizeof(long long));
 		return 0;
 	}
 	default: return setError(B2HIP_ERR_INVALID, "bad array id");

@@ -727,6 +727,7 @@ static int stepEndImpl(b2hip_world* w)
 		w->last.toiOverflow = c.toiOverflow;
 		if (c.toiOverflow) return setError(B2HIP_ERR_CAPACITY, "TOI event scratch overflow (flags " + std::to_string(c.toiOverflow) + ")");
 	}
+	w->contactsKnown = true; // (the read-back was the last thing on the stream, and the step has passed every check above)
 	if (w->sp.dt > 0.0f) w->inv_dt0 = w->sp.inv_dt;
 	// b2World::m_stepComplete (b2World.cpp:1072, 1084): only SolveTOI changes it
 	if (w->def.continuous && w->sp.dt > 0.0f) w->stepComplete = c.toiIncomplete == 0;

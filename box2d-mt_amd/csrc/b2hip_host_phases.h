@@ -214,6 +214,7 @@ static int growPairBuffers(b2hip_world* w)
 
 static int findNewContacts(b2hip_world* w, bool sync)
 {
+	w->contactsKnown = false; // (until the read-back behind it: contacts and TOI candidates are created)
 	for (int attempt = 0; sync && attempt < 4; ++attempt)
 	{
 		int rc = findNewContactsOnce(w, true);
@@ -297,6 +298,42 @@ static int phaseCollide(b2hip_world* w)
 	// (bit 2: the records of a workgroup's first contact staged in LDS, two staged 4-gons evaluated with unrolled loops -
 	// b2d_kernels_collide.h; Tumbler 316: 2.95 -> 2.88 ms. B2HIP_COLLIDE_UNI=0: off, the comparison form of the tests)
 	const int uni = w->collideUniOff ? 0 : 4;
+	// (the form that stores the compacted contact array itself, b2d_kernels_collide.h: k_collide<0, false, true> - in place of the split
+	// form and the three launches behind it, when nothing addresses a contact by its old index afterwards: no TOI candidate
+	// alive whose death would be replayed, no PreSolve records, no end events, no other rank. The host must know the contact
+	// count - the launch is one workgroup per chunk - and that no candidate is alive: both as of the last read-back, with
+	// nothing queued since that changes either.)
+	const bool known = w->contactsKnown;
+	w->contactsKnown = false;
+	bool compact = w->collideCompactOn && split && !stage && sort == 0 && known && w->h_dstate->c.nToiOrder == 0 && w->h_dstate->c.nContacts >= 0 &&
+		!d.preSolveOn && !d.eventsOn && !w->spatial && d.shardCount <= 1 && (unsigned)d.capContacts <= TREE_SUM_MAX;
+	if (compact)
+	{
+		hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+		(void)hipStreamIsCapturing(w->stream, &capturing);
+		compact = capturing == hipStreamCaptureStatusNone; // (a captured launch would replay its tag)
+	}
+	const size_t chunks = compact ? ((size_t)w->h_dstate->c.nContacts + w->collideChunk - 1) / w->collideChunk : 0;
+	if (compact && (chunks > w->collideCounts.cap || chunks / COLLIDE_GROUP + 1 > w->collideGroups.cap)) compact = false;
+	if (compact)
+	{
+		if (w->collideEpoch >= 0xffffu)
+		{
+			// (the tag is about to wrap: no word of 65 535 launches ago may read as published - as radixSort's)
+			HIP_TRY(hipMemsetAsync(w->collideCounts.p, 0, w->collideCounts.cap * sizeof(unsigned), w->stream));
+			HIP_TRY(hipMemsetAsync(w->collideGroups.p, 0, w->collideGroups.cap * sizeof(unsigned), w->stream));
+			w->collideEpoch = 0u;
+		}
+		CollideCompactArgs cc;
+		cc.counts = w->collideCounts.p;
+		cc.groups = w->collideGroups.p;
+		cc.abortWord = w->scanCtx.abortWord;
+		cc.tag = ++w->collideEpoch;
+		cc.chunk = w->collideChunk;
+		w->statCollideCompact += 1;
+		LAUNCH(w, (k_collide<0, false, true>), (int)std::max<size_t>(chunks, 1), 256, d, uni, cc);
+		return ktBracket(w, 2, 5);
+	}
 	if (stage) LAUNCH(w, (k_collide<1, true>), gridFor(d.capContacts), 256, d, sort);
 	else if (split)
 	{

@@ -261,6 +261,13 @@ struct b2hip_world
 	int collideStage = -1;       // B2HIP_COLLIDE_STAGE=0 / 1: never / always stage the shape records through LDS (default: by the record count)
 	int solidRoundsEnv = 0;      // B2HIP_SOLID_ROUNDS=1 / 2 / 4 / 8: the tile of the island build's passes over the contacts (x 256 contacts), else by the contact count
 	int collideSplitEnv = -1;    // B2HIP_COLLIDE_SPLIT=0 / 1: k_collide with the TOI-order replay inside / as a launch of its own (four waves per SIMD), else by the contact count
+	// k_collide<0, false, true> (b2d_kernels_collide.h): the narrow phase stores the compacted contact array itself
+	bool collideCompactOn = true;  // B2HIP_COLLIDE_COMPACT=0: never (the scan of the keep flags and k_compact_contacts behind every narrow phase)
+	int collideChunk = 256;        // contacts per workgroup of that form (B2HIP_TEST_COLLIDE_CHUNK: fewer, so that a small world has many chunks and groups of chunks)
+	bool contactsKnown = false;    // h_dstate holds the contact count and the TOI slot count as they are on the device: true behind a step's last read-back and behind applyEditOps', false once a narrow phase or a pair update is queued
+	DevArray<unsigned> collideCounts, collideGroups; // its status words, a chunk's count / a group's sum each
+	unsigned collideEpoch = 0;     // tag of its last launch (16 bits, never 0)
+	long long statCollideCompact = 0; // narrow phases that took that form since the world was created (b2hip_debug_read 24)
 	bool collideUniOff = false;  // B2HIP_COLLIDE_UNI=0: k_collide reads every shape record from memory (no staged pair of records)
 	int collideSortEnv = -1;     // B2HIP_COLLIDE_SORT=0 / 1: k_collide never / always sorts the contacts of a tile by shape-pair class in LDS
 	hipStream_t stream2 = nullptr; // small-island solver beside the large-island one
@@ -821,6 +828,8 @@ static void readSwitches(b2hip_world* w)
 	w->profileDetail = envInt("B2HIP_PROFILE_DETAIL", 1) != 0;
 	if (const char* e = getenv("B2HIP_SOLID_ROUNDS")) { const int v = atoi(e); w->solidRoundsEnv = (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0; }
 	w->collideSplitEnv = envInt("B2HIP_COLLIDE_SPLIT", -1);
+	w->collideCompactOn = envInt("B2HIP_COLLIDE_COMPACT", 1) != 0;
+	w->collideChunk = std::min(std::max(envInt("B2HIP_TEST_COLLIDE_CHUNK", 256), 1), 256);
 	w->collideUniOff = envInt("B2HIP_COLLIDE_UNI", 1) == 0;
 	w->collideSortEnv = envInt("B2HIP_COLLIDE_SORT", -1);
 	w->sortOnepass = envInt("B2HIP_SORT_ONEPASS", 1) != 0;
@@ -967,6 +976,14 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 		ENS(radixGlobalHist, 2 * RADIX_MAX_PASSES * RADIX_DIGITS);
 	}
 	ENS(keepFlag, cc + 1); ENS(keepScan, cc + 2);
+	if (w->collideCompactOn)
+	{
+		// (status words of k_collide<0, false, true> for every chunk the contact array can hold; a grown array starts from zeroed words
+		// under the running tag, which no word carries yet)
+		const size_t chunks = cc / (size_t)w->collideChunk + 2;
+		rc = w->collideCounts.ensure(chunks, s, false); if (rc) return rc;
+		rc = w->collideGroups.ensure(chunks / COLLIDE_GROUP + 2, s, false); if (rc) return rc;
+	}
 	ENS(toiList, cc); ENS(toiPos2c, cc); ENS(toiDestroyList, cc); ENS(toiNewList, TOI_NEW_LIST_MAX);
 	ENS(b_toiGroup, nb); ENS(toiGroups, nb); ENS(toiGroupCount, std::min<size_t>(nb, TOI_GROUPS_MAX)); ENS(toiGroupList, std::min<size_t>(nb, TOI_GROUPS_MAX) * CHAIN_ADJ_MAX); ENS(toiMoved, TOI_MOVED_ALL_MAX); ENS(toiNew, 8 * TOI_NEWPAIR_MAX); ENS(toiParent, nb); ENS(toiDomOf, nb); ENS(toiDomRoot, TOI_DOMAINS_MAX); ENS(toiDomCount, TOI_DOMAINS_MAX); ENS(toiDomBase, TOI_DOMAINS_MAX); ENS(toiDomFill, TOI_DOMAINS_MAX); ENS(toiDomFailed, TOI_DOMAINS_MAX); ENS(toiDomEvents, TOI_DOMAINS_MAX); ENS(toiDomList, cc); ENS(toiHull, np); ENS(snapBody, 5 * nb); ENS(snapFat, np);
 	{
@@ -1435,6 +1452,7 @@ static int applyEditOps(b2hip_world* w, bool betweenSteps)
 	rc = readState(w); // (also makes the staging vector reusable, and the state rows above readable)
 	if (rc) return rc;
 	w->editOps.clear();
+	w->contactsKnown = true; // (read back behind everything that was queued)
 	w->lastContacts = w->h_dstate->c.nContacts;
 	w->last.nContacts = w->lastContacts;
 	return 0;
