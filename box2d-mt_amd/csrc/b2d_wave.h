@@ -149,29 +149,6 @@ __device__ __forceinline__ void blockMaxU32Flush(const BlockMaxU32& run, uint32_
 	if (!s_one) waveAtomicMaxU32Guarded(base, run.key, run.val, have);
 }
 
-// Counters every lane of a kernel adds to (island and contact censuses): ONE atomic per workgroup. Same-address atomics are
-// served one after the other in L2, ~6-10 ns each - one per wave of a pass over a million bodies is 16 000 of them, 100 us
-// and more, longer than the pass itself. Every lane of the workgroup must call (barriers inside).
-__device__ __forceinline__ void blockAtomicAddInt2(int* a0, int v0, int* a1, int v1)
-{
-	__shared__ int s_sum[2];
-	if (threadIdx.x == 0) { s_sum[0] = 0; s_sum[1] = 0; }
-	__syncthreads();
-	v0 = waveSumInt(v0);
-	v1 = waveSumInt(v1);
-	if (waveLane() == 0)
-	{
-		if (v0) atomicAdd(&s_sum[0], v0);
-		if (v1) atomicAdd(&s_sum[1], v1);
-	}
-	__syncthreads();
-	if (threadIdx.x == 0)
-	{
-		if (s_sum[0]) atomicAdd(a0, s_sum[0]);
-		if (s_sum[1]) atomicAdd(a1, s_sum[1]);
-	}
-}
-
 // A running maximum many waves offer to: most offers do not raise it - look first (a plain load), add to the queue of the
 // word's atomics only then. (The value only grows while the kernel runs: a stale read can cost an atomic, never lose a maximum.)
 __device__ __forceinline__ void atomicMaxIfAbove(int* addr, int v)
@@ -251,7 +228,8 @@ __device__ __forceinline__ void blockHotFlush(BlockHot* h, int* base)
 }
 
 // Slots of ONE shared cursor for the valid lanes of a whole workgroup: one global atomicAdd per workgroup and call instead of
-// one per wave. Every thread of the workgroup must call it (barriers inside); slots are handed out in lane order.
+// one per wave. Every thread of the workgroup must call it (barriers inside); slots are handed out in lane order, a lane
+// that is not valid gets 0 like the other allocators' (not the slot of the valid lane behind it).
 __device__ __forceinline__ int blockAlloc(int* cursor, bool valid)
 {
 	__shared__ int s_wave[16], s_base;
@@ -267,7 +245,7 @@ __device__ __forceinline__ int blockAlloc(int* cursor, bool valid)
 		s_base = run > 0 ? atomicAdd(cursor, run) : 0;
 	}
 	__syncthreads();
-	return s_base + s_wave[wv] + __popcll(m & ((1ull << lane) - 1ull));
+	return valid ? s_base + s_wave[wv] + __popcll(m & ((1ull << lane) - 1ull)) : 0;
 }
 
 // Every valid lane gets a unique slot of counter[key]: one atomicAdd per distinct key per wave.
@@ -337,7 +315,8 @@ __device__ __forceinline__ int waveKeyedAllocOnce(int* counter, int key, bool va
 	return valid ? base + __popcll(peers & ((1ull << lane) - 1ull)) : 0;
 }
 
-// The same for a whole 256-lane workgroup and keys in [0, 64]: ranks through an LDS histogram, then ONE global atomicAdd
+// The same for a whole workgroup of at least 65 threads (the first 65 clear and flush the LDS counters; both callers run with
+// 256) and keys in [0, 64]: ranks through an LDS histogram, then ONE global atomicAdd
 // per key that occurs, all of them in flight together (waveKeyedAlloc pays one atomic round trip per distinct key and
 // wave, one after the other: seven colours on the 10k-body pyramid made k_color_fill 24 us). Every thread of the
 // workgroup must call it (it contains barriers). `fetch` = false: only count (no slot returned).

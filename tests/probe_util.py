@@ -1,4 +1,5 @@
-"""Helpers to build ShapeRec blobs (box2d-mt_amd/csrc/b2d_collide.h) for the CPU probe of the device math."""
+"""Helpers to build ShapeRec blobs (box2d-mt_amd/csrc/b2d_collide.h) for the CPU probe of the device math, and the loaders of
+the probe libraries."""
 import ctypes as C
 import os
 import subprocess
@@ -10,6 +11,7 @@ PROBE_SRC = os.path.join(ROOT, "tests", "probe", "host_probe.cpp")
 PROBE_CASES = os.path.join(ROOT, "tests", "probe", "probe_cases.h")
 PROBE_LIB = os.path.join(ROOT, "tests", "probe", "libhost_probe.so")
 DEVICE_PROBE_LIB = os.path.join(ROOT, "tests", "probe", "libdevice_probe.so")
+PRIMS_PROBE_LIB = os.path.join(ROOT, "tests", "probe", "libprims_probe.so")
 
 CIRCLE, EDGE, POLYGON = 0, 1, 2
 
@@ -22,6 +24,25 @@ def build_probe():
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
                                "-I", os.path.join(ROOT, "box2d-mt_amd", "csrc"), "-o", PROBE_LIB, PROBE_SRC])
     return C.CDLL(PROBE_LIB)
+
+
+def load_prims_probe():
+    """tests/probe/prims_probe.hip through ctypes (built by `make -C box2d-mt_amd all`; the caller checks that the file exists
+    and has called b2hip.use_torch_hip_runtime()). Every entry returns 0 or a hipError_t, pprobe_scan_run also
+    pprobe_scan_aborted_code()."""
+    L = C.CDLL(PRIMS_PROBE_LIB)
+    ip, up = C.POINTER(C.c_int), C.POINTER(C.c_uint32)
+    L.pprobe_scan_aborted_code.restype = C.c_int
+    L.pprobe_scan_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.pprobe_scan_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.pprobe_scan_epoch.argtypes = [C.c_void_p]
+    L.pprobe_scan_epoch.restype = C.c_uint
+    L.pprobe_scan_set_epoch.argtypes = [C.c_void_p, C.c_uint]
+    L.pprobe_scan_close.argtypes = [C.c_void_p]
+    L.pprobe_wave.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, up, ip, up, C.c_int, ip, C.c_int, C.c_int]
+    for name in ("pprobe_scan_open", "pprobe_scan_run", "pprobe_scan_set_epoch", "pprobe_scan_close", "pprobe_wave"):
+        getattr(L, name).restype = C.c_int
+    return L
 
 
 def shape_rec(kind, count=0, radius=0.0, centroid=(0, 0), verts=(), normals=()):
