@@ -41,6 +41,7 @@
 // consecutive pieces of what used to be one 6 400-line file and share its scope) ------------------------------------------
 #include "b2hip_host_world.h"
 #include "b2hip_host_phases.h"
+#include "b2hip_host_toi.h"
 
 extern "C"
 {

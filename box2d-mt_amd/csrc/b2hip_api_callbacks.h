@@ -190,6 +190,11 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 //     key, [10] slots in use now (live + tombstones), [11] the mask now.
 // 24: one long long: narrow phases since the world was created in which k_collide<0, false, true> stored the compacted contact
 //     array itself (no scan of the keep flags, no k_compact_contacts behind it).
+// 25: the host side of SolveTOI since the world was created (ToiStats), `count` (<= 10) long longs from `first`. Runs of the
+//     phase that had impacts pending, by path: [0] chains queued without the first pass's census, [1] chains after it,
+//     [2] components queued without it, [3] components after it, [4] the serial loop chosen from it (second runs count under
+//     [1], [3], [4] again). Rungs of the fall-back ladder: [5] redo behind a late pair sort, [6] chains again with the hash grid,
+//     [7] serial replay (toi_serial_fallbacks), [8] re-run after a full contact array, [9] PreSolve re-run (toi_pre_solve_reruns).
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -252,6 +257,12 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 	{
 		if (first != 0 || count != 1) return setError(B2HIP_ERR_INVALID, "narrow-phase statistics: [0, 1)");
 		memcpy(out, &w->statCollideCompact, sizeof(long long));
+		return 0;
+	}
+	case 25:
+	{
+		if (first < 0 || count < 0 || first + count > ToiStats::N) return setError(B2HIP_ERR_INVALID, "TOI host statistics: [0, 10)");
+		memcpy(out, w->toiStats.n + first, (size_t)count * sizeof(long long));
 		return 0;
 	}
 	default: return setError(B2HIP_ERR_INVALID, "bad array id");
@@ -446,7 +457,7 @@ int b2hip_get_counters(b2hip_world* w, b2hip_counters* out)
 	out->toi_events = w->last.nToiEvents;
 	out->toi_calls = w->last.nToiCalls;
 	out->toi_pending_first_pass = w->last.nToiList;
-	out->toi_serial_fallbacks = w->toiFallbacks;
+	out->toi_serial_fallbacks = (int)w->toiStats.n[ToiStats::SerialFallback];
 	out->blocks = w->last.nBlocks;
 	out->cut_constraints = w->last.nCutRows;
 	out->block_max_rows = w->last.blkMaxRows;
@@ -457,8 +468,8 @@ int b2hip_get_counters(b2hip_world* w, b2hip_counters* out)
 	out->hub_constraints = w->last.nHubRows;
 	out->hub_fixpoint_rounds = w->last.hubRounds;
 	out->hub_serial_chunks = w->last.hubSerialChunks;
-	out->toi_chain_contacts = w->toiChainContacts;
-	out->toi_pre_solve_reruns = w->toiPreSolveReruns;
+	out->toi_chain_contacts = (int)w->toiStats.chainContacts;
+	out->toi_pre_solve_reruns = (int)w->toiStats.n[ToiStats::PreSolveRerun];
 	out->solver_recoveries = w->solverRecoveries + w->colorRecoveries;
 	return 0;
 }

@@ -277,13 +277,13 @@ static int spExchangeState(b2hip_world* w, int mode)
 		if (rc) return rc;
 		rc = spPrepareSend(w);
 		if (rc) return rc;
-		if (mode == 0 || w->toiSnapshotTaken)
+		if (mode == 0 || w->toiStep.snapshotTaken)
 			LAUNCH(w, k_sp_export_state, gridFor(std::max(d.nBodies, d.capMoves)), 256, d, w->spSend.p, mode, capB, capP);
 		if (mode == 1)
 		{
 			// the contacts this rank's TOI phase created (behind the array all ranks shared when the phase began): their
 			// descriptors, for the merge of the tails; header words 5 and 6 = how many, how many of them with another rank's body
-			LAUNCH(w, k_sp_export_tail, gridFor(capT), 256, d, w->spSend.p + tailAt, w->spSend.p, w->spContactsBeforeToi, capT, w->toiChains ? 1 : 0, (int*)(w->spVirt.p + SP_TAIL_MAX));
+			LAUNCH(w, k_sp_export_tail, gridFor(capT), 256, d, w->spSend.p + tailAt, w->spSend.p, w->spContactsBeforeToi, capT, w->toiStep.verdictPending() ? 1 : 0, (int*)(w->spVirt.p + SP_TAIL_MAX));
 		}
 		rc = spAllGather(w, words);
 		if (rc) return rc;
@@ -303,11 +303,7 @@ static int spExchangeState(b2hip_world* w, int mode)
 				// this rank's own phase, as its header shows it (what a read-back before the exchange would have said)
 				const int* mine = hdr[d.shardRank];
 				if (mine[7] & 0x40000000) return setError(B2HIP_ERR_CAPACITY, "contact array full during a TOI sub-step of a spatially sharded world");
-				if (w->toiChains)
-				{
-					if (mine[4] > 0) w->toiGridSticky = 16;
-					else if (w->toiGridSticky > 0 && !w->spToiSettled) w->toiGridSticky -= 1;
-				}
+				toiGridHint(w, mine[4], !w->spToiSettled); // (see toiSettle)
 				w->spToiUnsafe = mine[7] & 0x3fffffff;
 				bool any = false;
 				for (int r = 0; r < ranks; ++r) any = any || (hdr[r][7] & 0x3fffffff) != 0;
@@ -335,7 +331,11 @@ static int spExchangeState(b2hip_world* w, int mode)
 				// an event reached over an ownership boundary: every rank takes its phase back, the components of such pairs
 				// merge as if the contact existed, and the phase runs again (the pair lies inside one rank then)
 				if (nVirt > SP_TAIL_MAX) return setError(B2HIP_ERR_CAPACITY, "more than 4 096 TOI conflicts between the ranks of a spatially sharded world");
-				if (w->toiSnapshotTaken) LAUNCH(w, k_toi_snapshot, gridFor(std::max(d.nBodies, d.capContacts)), 256, d, 1);
+				if (w->toiStep.snapshotTaken)
+				{
+					rc = toiSnapshot(w, w->stream, ToiSnap::Restore);
+					if (rc) return rc;
+				}
 				rc = spResolve(w, nVirt);
 				if (rc) return rc;
 				w->spToiRedos += 1;
@@ -538,41 +538,24 @@ static int spResolve(b2hip_world* w, int nVirt)
 	return setError(B2HIP_ERR_INVALID, "straddling contacts remain after a resolution of a spatially sharded world");
 }
 
-// Behind SolveTOI: this rank's phase is settled here (the fallbacks b2hip_step_end would run), then E4.
+// Behind SolveTOI: this rank's phase is settled here (the ladder b2hip_step_end runs for an unsharded world), then E4.
 static int spAfterToi(b2hip_world* w)
 {
-	// (what b2hip_step_end does for an unsharded world's parallel TOI paths - the grid's stickiness, the second run of the
-	// chains with the grid, the serial replay - happens here, before the other ranks take this rank's result: the counters
-	// that decide it travel in this rank's own header, so the usual step costs no read-back of its own)
+	// (what b2hip_step_end does for an unsharded world's parallel TOI paths - toiSettle: the second run of the chains with
+	// the grid, the serial replay - happens here, before the other ranks take this rank's result: the counters that decide
+	// it travel in this rank's own header, so the usual step costs no read-back of its own)
 	w->spToiSettled = false;
 	for (int attempt = 0; attempt < 6; ++attempt)
 	{
 		int rc = spExchangeState(w, 1);
-		if (rc != 2) { w->toiChains = false; w->toiSpeculative = false; return rc; }
-		// (whichever parallel path this rank's phase took: unsafe with toiChains false - the components - used to do nothing
-		// here for six exchanges and then fail the step)
+		if (rc != 2) { w->toiStep.dropVerdict(); return rc; } // (nothing is left for b2hip_step_end's own toiSettle)
+		// Some rank's parallel path - chains or components - met an order-dependent case. This rank's header carries its own
+		// bits only while its verdict is pending (k_sp_export_tail: hdr[7] = chains ? toiUnsafe : 0, and spExchangeState passes
+		// ToiStep::verdictPending() for `chains`): toiSettle relies on it when it leaves early without a pending verdict.
 		if (w->spToiUnsafe != 0)
 		{
-			LAUNCH(w, k_toi_snapshot, gridFor(std::max(w->dw.nBodies, w->dw.capContacts)), 256, w->dw, 1);
-			bool serial = true;
-			if (w->toiChains && w->spToiUnsafe == 4 /* TOI_UNSAFE_PAIR */ && !w->toiChainsHadGrid && !w->dw.noChainCreate)
-			{
-				// a chain moved a proxy out of its fat AABB while the hash grid was not kept up: the chains once more, with the grid
-				w->toiGridSticky = 16;
-				w->toiChains = false;
-				w->toiCountersFresh = false;
-				rc = phaseToiSync(w);
-				if (rc) return rc;
-				w->toiGridRetries += 1;
-				serial = false; // (its outcome comes with the next exchange's headers)
-			}
-			if (serial)
-			{
-				rc = toiSerial(w); // (toiChains = false: nothing left to be unsafe about)
-				if (rc) return rc;
-				w->toiFallbacks += 1;
-				w->toiSyncSticky = 16;
-			}
+			rc = toiSettle(w, w->spToiUnsafe, true);
+			if (rc) return rc;
 			w->spToiSettled = true;
 		}
 	}

@@ -1,5 +1,5 @@
 // b2hip_api_step.h - part of the ONE translation unit b2hip.hip, inside its extern "C" block: b2hip_step and its phase entry
-// points, the end of a step (fallbacks of the parallel TOI paths, profile, counters), state / contact event getters.
+// points, the end of a step (read-back, late pair update, the listener's records, profile, counters; the TOI phase's part: b2hip_host_toi.h), state / contact event getters.
 // (No include guard on purpose: b2hip.hip includes it exactly once, in order - the fragments share one scope.)
 
 int b2hip_step_begin(b2hip_world* w, float dt, int velocity_iterations, int position_iterations)
@@ -11,20 +11,6 @@ int b2hip_step_begin(b2hip_world* w, float dt, int velocity_iterations, int posi
 }
 
 static bool keyLess(const std::pair<unsigned long long, int>& a, const std::pair<unsigned long long, int>& b) { return a < b; }
-
-static void toManifold(b2hip_manifold* m, float4 m0, float4 m1, float4 imp, int4 m3)
-{
-	m->type = m3.z;
-	m->point_count = m3.w;
-	m->local_normal[0] = m0.x; m->local_normal[1] = m0.y;
-	m->local_point[0] = m0.z; m->local_point[1] = m0.w;
-	m->point_local[0][0] = m1.x; m->point_local[0][1] = m1.y;
-	m->point_local[1][0] = m1.z; m->point_local[1][1] = m1.w;
-	m->normal_impulse[0] = imp.x; m->tangent_impulse[0] = imp.y;
-	m->normal_impulse[1] = imp.z; m->tangent_impulse[1] = imp.w;
-	m->id_key[0] = (uint32_t)m3.x;
-	m->id_key[1] = (uint32_t)m3.y;
-}
 
 static int collideImpl(b2hip_world* w)
 {
@@ -225,11 +211,7 @@ int b2hip_find_new_contacts(b2hip_world* w)
 
 static int solveToiImpl(b2hip_world* w)
 {
-	w->toiRan = false;
-	w->toiChains = false;
-	w->toiSpeculative = false;
-	w->toiSnapshotTaken = false;
-	w->toiVerdicts.clear();
+	w->toiStep.begin();
 	w->dw.nToiVerdict = 0;
 	w->last.nToiList = w->last.nToiCalls = w->last.nToiEvents = 0;
 	if (w->def.continuous && w->sp.dt > 0.0f)
@@ -243,13 +225,15 @@ static int solveToiImpl(b2hip_world* w)
 			if (rc <= 0) { if (rc) return rc; break; }
 			// (1: an event reached over an ownership boundary - the phase was taken back and the owners merged: once more)
 			if (attempt == 8) return setError(B2HIP_ERR_INVALID, "the TOI phase of a spatially sharded world keeps reaching over ownership boundaries");
-			w->toiRan = false; w->toiChains = false; w->toiSpeculative = false; w->toiSnapshotTaken = false; w->toiCountersFresh = false;
-			rc = phaseToi(w);
+			// (a new phase, with a snapshot of its own: begin() - the PreSolve answers it also drops a sharded world has
+			// none of, it takes no listener. A sharded world's phaseToi is phaseToiSync.)
+			w->toiStep.begin();
+			rc = toiRunAgain(w);
 			if (rc) return rc;
 		}
 	}
 	stampPhase(w, 12);
-	w->toiEventValid = true;
+	w->toiHints.eventValid = true;
 	return 0;
 }
 
@@ -260,8 +244,6 @@ int b2hip_solve_toi(b2hip_world* w)
 	DEVICE_GUARD(w);
 	return stepFailed(w, solveToiImpl(w));
 }
-
-static int uploadToiVerdicts(b2hip_world* w);
 
 // B2HIP_HANDOVER_WHY=1: what the lane that gave up first was waiting for (b2d_handover.h: dataflowRun), and every constraint
 // row of the large islands that touches either of its two bodies - colour, the block segment it was placed in, the bodies'
@@ -348,150 +330,6 @@ static void handoverPostMortem(b2hip_world* w)
 	}
 }
 
-// A contact created inside a TOI sub-step did not fit the array (whatever path ran last, fallbacks included): never a
-// silent drop. With the snapshot of this step's TOI phase at hand the phase is undone, the array doubled and the phase
-// run again; without one (serial-only mode) it is an error.
-static int settleToiOverflow(b2hip_world* w)
-{
-	int rc = 0;
-	for (int attempt = 0; (w->h_dstate->c.overflow & 1) != 0; ++attempt)
-	{
-		if (!w->toiSnapshotTaken || attempt == 3) return setError(B2HIP_ERR_CAPACITY, "contact array full during a TOI sub-step");
-		// (edits can only be pending here if a PreSolve called from a sub-step made them: toiPreSolveRounds)
-		if (!w->dirtyList.empty() || !w->editOps.empty() || !w->proxyEdits.empty() || !w->pendingMoves.empty())
-			return setError(B2HIP_ERR_CAPACITY, "contact array full during a TOI sub-step whose PreSolve edited the world");
-		LAUNCH(w, k_toi_snapshot, gridFor(std::max(w->dw.nBodies, w->dw.capContacts)), 256, w->dw, 1);
-		rc = ensureCapacity(w, 2 * (size_t)w->dw.capContacts);
-		if (rc) return rc;
-		rc = uploadToiVerdicts(w);
-		if (rc) return rc;
-		HIP_TRY(hipMemsetAsync(&w->d_state.p->c.overflow, 0, sizeof(int), w->stream));
-		w->toiChains = false;
-		w->toiSpeculative = false;
-		rc = phaseToiSync(w);
-		if (rc) return rc;
-		if (w->toiChains)
-		{
-			// (the parallel paths report through toiUnsafe: take their serial fallback here as well)
-			rc = downloadState(w, -1);
-			if (rc) return rc;
-			if (w->h_dstate->c.toiUnsafe != 0)
-			{
-				LAUNCH(w, k_toi_snapshot, gridFor(std::max(w->dw.nBodies, w->dw.capContacts)), 256, w->dw, 1);
-				rc = toiSerial(w);
-				if (rc) return rc;
-				w->toiFallbacks += 1;
-			}
-		}
-		rc = downloadState(w, -1);
-		if (rc) return rc;
-	}
-	return 0;
-}
-
-// The answers collected so far go to the device before the phase runs again (DW::toiVerdict, DW::nToiVerdict).
-static int uploadToiVerdicts(b2hip_world* w)
-{
-	const size_t n = std::min(w->toiVerdicts.size(), w->toiVerdict.cap);
-	w->dw.nToiVerdict = w->dw.toiVerdict != nullptr ? (int)n : 0;
-	if (w->dw.nToiVerdict > 0) HIP_TRY(hipMemcpyAsync((void*)w->toiVerdict.p, w->toiVerdicts.data(), n * sizeof(int4), hipMemcpyHostToDevice, w->stream));
-	return 0;
-}
-
-static void toiCallbackFromLog(const ToiLogRec& r, b2hip_toi_callback* cb)
-{
-	memset(cb, 0, sizeof(*cb));
-	cb->kind = r.info.x;
-	cb->contact_index = r.info.y;
-	cb->fixture_a = r.info.z;
-	cb->fixture_b = r.info.w;
-	toManifold(&cb->old_manifold, r.o0, r.o1, r.oimp, r.o3);
-	toManifold(&cb->manifold, r.n0, r.n1, r.nimp, r.n3);
-	cb->material.friction = r.mat.x;
-	cb->material.restitution = r.mat.y;
-	cb->material.tangent_speed = r.mat.z;
-}
-
-// b2ContactListener::PreSolve from INSIDE the TOI sub-steps (b2World.cpp:866,946 -> b2Contact::Update -> b2Contact.cpp:283-297).
-// The reference calls it in the middle of its event loop, and what it does to the contact changes that sub-step: a contact
-// switched off keeps the sweeps of its bodies and stays out of the sub-step's island (b2World.cpp:873-881, 948-954), an
-// edited material is what the sub-step's solver reads. The event loop here is one kernel, so the phase is run to its end,
-// its log (DW::toiLog: the Updates in the reference's call order) read, and PreSolve called for the logged Updates in
-// order - each exactly once. An answer that changes nothing needs nothing: the contact stays on (or off, where the sub-step
-// assumed the listener's last answer for this contact: CF_PRESOLVE_OFF, toiPreSolveOutcome) and its material as it was. The
-// first one that does makes everything after it void: the phase goes back to its snapshot and runs again with the
-// answers so far on the device (the loop applies them at the same log slots - it is deterministic, so the log repeats
-// itself up to there), and the calls go on behind the slot that was answered. One extra run of the phase per changing answer.
-static int toiPreSolveRounds(b2hip_world* w, std::vector<ToiLogRec>& recs)
-{
-	int asked = 0; // log slots whose PreSolve has been called
-	for (int round = 0;; ++round)
-	{
-		const int n = std::min(w->h_dstate->c.nToiLog, w->dw.capToiLog);
-		recs.resize((size_t)std::max(n, 0));
-		if (n > 0) HIP_TRY(hipMemcpy((void*)recs.data(), w->toiLog.p, (size_t)n * sizeof(ToiLogRec), hipMemcpyDeviceToHost));
-		if (!hasPreSolve(w) || w->dw.toiVerdict == nullptr) return 0;
-		// (the log itself was cut short: no listener call from a truncated log - the step fails with the capacity error below)
-		if (w->h_dstate->c.toiOverflow & 64) return 0;
-		// The callbacks below may edit bodies (callbackWindow). h_state holds the state AFTER this step's phases by now, but the
-		// mirror's epoch is only advanced at the very end of the step (refreshMirror): a body the host had touched before the
-		// step (a force applied every frame) would not be pulled again and the edit would land on - and later upload - its
-		// pre-step row. The read-back that just happened is the mirror from here on.
-		if (n > asked) refreshMirror(w);
-		bool again = false;
-		for (int k = asked; k < n && !again; ++k)
-		{
-			const ToiLogRec& r = recs[(size_t)k];
-			int4 v = make_int4(0, 0, 0, 0);
-			if (r.info.x & 4)
-			{
-				b2hip_toi_callback cb;
-				toiCallbackFromLog(r, &cb);
-				b2hip_pre_solve_record rec;
-				rec.contact_index = cb.contact_index;
-				rec.fixture_a = cb.fixture_a;
-				rec.fixture_b = cb.fixture_b;
-				rec.enabled = 1;
-				rec.old_manifold = cb.old_manifold;
-				rec.manifold = cb.manifold;
-				rec.material = cb.material;
-				// (world edits made from the callback are taken like edits between steps: they reach the device before the next step)
-				w->callbackWindow = true;
-				if (w->preSolveBatchFn) w->preSolveBatchFn(w->preSolveUser, 1, &rec);
-				else rec.enabled = w->preSolveFn(w->preSolveUser, rec.contact_index, rec.fixture_a, rec.fixture_b, &rec.old_manifold, &rec.manifold, &rec.material) ? 1 : 0;
-				w->callbackWindow = false;
-				int bits[3];
-				memcpy(bits, &rec.material, sizeof(bits));
-				v = make_int4(1 | (rec.enabled ? 0 : 2), bits[0], bits[1], bits[2]);
-				// (bit 4 of the kind: the sub-step went on as if the contact had been switched off - the listener's last answer)
-				const bool assumedOff = (r.info.x & 16) != 0;
-				again = (rec.enabled != 0) == assumedOff || memcmp(&rec.material.friction, &r.mat.x, 4) != 0 || memcmp(&rec.material.restitution, &r.mat.y, 4) != 0 ||
-					memcmp(&rec.material.tangent_speed, &r.mat.z, 4) != 0;
-			}
-			w->toiVerdicts.push_back(v);
-			asked = k + 1;
-		}
-		if (!again) return 0;
-		if (!w->toiSnapshotTaken) return setError(B2HIP_ERR_INVALID, "PreSolve changed a contact inside a TOI sub-step, and the phase kept no snapshot");
-		if (round >= w->dw.capToiLog) return setError(B2HIP_ERR_INVALID, "TOI PreSolve rounds do not end");
-		// (the host mirror of an edited body was refreshed from the state that is about to be taken back)
-		if (!w->dirtyList.empty() || !w->editOps.empty() || !w->proxyEdits.empty() || !w->pendingMoves.empty())
-			return setError(B2HIP_ERR_INVALID, "a PreSolve inside a TOI sub-step edited the world AND changed its contact: not supported");
-		LAUNCH(w, k_toi_snapshot, gridFor(std::max(w->dw.nBodies, w->dw.capContacts)), 256, w->dw, 1);
-		int rc = uploadToiVerdicts(w);
-		if (rc) return rc;
-		w->toiChains = false;
-		w->toiSpeculative = false;
-		rc = phaseToiSync(w);
-		if (rc) return rc;
-		rc = downloadState(w, -1);
-		if (rc) return rc;
-		rc = settleToiOverflow(w);
-		if (rc) return rc;
-		w->toiPreSolveReruns += 1;
-	}
-}
-
 static int stepEndImpl(b2hip_world* w)
 {
 	int rc = downloadState(w, -1, w->sp.dt > 0.0f); // (rows only if this is the last read-back of the step: k_end_step)
@@ -510,12 +348,9 @@ static int stepEndImpl(b2hip_world* w)
 		if (w->h_dstate->c.nPairs > COUNT_RANK_MAX || pairOverflow)
 		{
 			w->pairsLargeSticky = 16; // (the next steps ask for the pair count right after the search: findNewContactsGraph)
-			const bool redoToi = w->toiSpeculative;
-			if (redoToi && w->h_dstate->c.nToiList > 0)
-			{
-				// the TOI phase ran without the contacts that are created only now: undo it
-				LAUNCH(w, k_toi_snapshot, gridFor(std::max(w->dw.nBodies, w->dw.capContacts)), 256, w->dw, 1);
-			}
+			// (a TOI phase queued without its census ran without the contacts that are created only now: undone, and redone behind them)
+			bool redoToi = false;
+			if ((rc = toiUndoBeforeLatePairs(w, redoToi))) return rc;
 			if (pairOverflow)
 			{
 				rc = growPairBuffers(w);
@@ -524,81 +359,14 @@ static int stepEndImpl(b2hip_world* w)
 			}
 			else rc = runSortAndCreate(w, true, w->h_dstate->c.nPairs);
 			if (rc) return rc;
-			if (redoToi)
-			{
-				w->toiChains = false;
-				w->toiSpeculative = false;
-				// (the redone phase is judged on its own: not by what the speculative launch assumed of the grid - ADVICE round 5)
-				w->toiSpecDomains = false;
-				w->toiSpecGridAssumed = false;
-				rc = phaseToiSync(w);
-				if (rc) return rc;
-			}
+			if (redoToi && (rc = toiRedoAfterLatePairs(w))) return rc;
 			rc = downloadState(w, -1);
 			if (rc) return rc;
 		}
 	}
-	if (w->toiSpeculative)
-	{
-		const Counters& tc = w->h_dstate->c;
-		if (tc.nToiList > w->dw.capContacts) return setError(B2HIP_ERR_CAPACITY, "TOI list overflow");
-		w->last.nToiList = tc.nToiList;
-		w->last.nToiCalls = tc.nToiCalls;
-		w->toiRan = tc.nToiList > 0;
-		if (tc.nToiList == 0) w->toiChains = false;
-	}
-	if (w->toiSpecDomains)
-	{
-		// the component path was queued without its census (phaseToi): the hints for the next step, and the one assumption
-		w->toiSpecDomains = false;
-		w->lastToiList = w->h_dstate->c.nToiList;
-		w->gridFreshLast = w->h_dstate->c.gridFresh != 0;
-		if (w->h_dstate->c.nToiList > 0) w->toiDomainsSticky = 16;
-		else if (w->toiDomainsSticky > 0) w->toiDomainsSticky -= 1;
-		// (the event loops searched a grid that this step's pair update had NOT rebuilt - nothing moved, the first step in
-		// many: as with any order-dependent case, back to the snapshot and the serial loop, which builds its own)
-		if (w->toiChains && w->toiSpecGridAssumed && w->h_dstate->c.gridFresh == 0) w->h_dstate->c.toiUnsafe |= 0x80;
-	}
-	if (w->toiChains)
-	{
-		if (w->h_dstate->c.nToiMoved > 0) w->toiGridSticky = 16;
-		else if (w->toiGridSticky > 0) w->toiGridSticky -= 1;
-	}
-	if (w->toiChains && w->h_dstate->c.toiUnsafe != 0)
-	{
-		// a chain met an order-dependent case: back to the state before the chains, then the reference's serial order
-		LAUNCH(w, k_toi_snapshot, gridFor(std::max(w->dw.nBodies, w->dw.capContacts)), 256, w->dw, 1);
-		if (w->h_dstate->c.toiUnsafe == 4 /* TOI_UNSAFE_PAIR */ && !w->toiChainsHadGrid && !w->dw.noChainCreate)
-		{
-			// ... unless all that happened is that a chain moved a proxy out of its fat AABB while the hash grid was not kept
-			// up (nothing had moved for 16 steps): the chains once more, with the grid - most such moves find nothing, or a
-			// pair the chains' close-out can create itself. (The serial loop costs ~50 us per event: 15 ms for the 290 resting
-			// impacts of a 50 000-box pyramid; this costs a second first pass.)
-			w->toiGridSticky = 16;
-			w->toiChains = false;
-			w->toiSpeculative = false;
-			w->toiSpecDomains = false;
-			w->toiSpecGridAssumed = false;
-			rc = phaseToiSync(w);
-			if (rc) return rc;
-			rc = downloadState(w, -1);
-			if (rc) return rc;
-			w->toiGridRetries += 1;
-			if (w->toiChains && w->h_dstate->c.toiUnsafe != 0) LAUNCH(w, k_toi_snapshot, gridFor(std::max(w->dw.nBodies, w->dw.capContacts)), 256, w->dw, 1);
-		}
-	}
-	if (w->toiChains && w->h_dstate->c.toiUnsafe != 0)
-	{
-		if (w->toiWhy) fprintf(stderr, "b2hip: TOI fallback to the serial loop, unsafe bits 0x%x (1 partner, 2 woke, 4 new pair, 8 capacity, 16 moved proxies), %d pending, %d components\n", w->h_dstate->c.toiUnsafe, w->h_dstate->c.nToiList, w->h_dstate->c.nToiDomains);
-		// (a capacity cut - possibly more candidate contacts in one event than the narrow component loops have lanes: the wide form next time)
-		if (w->h_dstate->c.toiUnsafe & 8) w->toiDomWide = 64;
-		rc = toiSerial(w);
-		if (rc) return rc;
-		w->toiFallbacks += 1;
-		w->toiSyncSticky = 16;
-		rc = downloadState(w, -1);
-		if (rc) return rc;
-	}
+	// the TOI phase: a parallel path's verdict, then a contact array that filled up inside a sub-step
+	rc = toiSettle(w, w->h_dstate->c.toiUnsafe, false);
+	if (rc) return rc;
 	rc = settleToiOverflow(w);
 	if (rc) return rc;
 	w->postSolve.clear();
@@ -718,8 +486,8 @@ static int stepEndImpl(b2hip_world* w)
 	w->last.nHubRows = c.nHubRows;
 	w->last.hubRounds = c.hubRounds;
 	w->last.hubSerialChunks = c.hubSerialChunks;
-	w->toiChainContacts += c.nToiChainCreated;
-	if (w->toiRan)
+	w->toiStats.chainContacts += c.nToiChainCreated;
+	if (w->toiStep.ran)
 	{
 		w->last.toiUnsafe = c.toiUnsafe;
 		w->last.nToiEvents = c.nToiEvents;
@@ -756,7 +524,7 @@ static int stepEndImpl(b2hip_world* w)
 	p[10] = bp0;                                                                 // broadphaseSyncFixtures
 	p[11] = bp1 + bpTop;                                                         // broadphaseFindContacts
 	p[9] = bp0 + bp1 + bpTop;                                                    // broadphase
-	if (w->toiEventValid) p[7] = span(10, 12);                                   // solveTOI
+	if (w->toiHints.eventValid) p[7] = span(10, 12);                                   // solveTOI
 	w->solverMs = small + large;
 	if (w->blocksThisStep && w->h_dstate->stamps[4] > 0)
 	{

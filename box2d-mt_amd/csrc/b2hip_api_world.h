@@ -75,8 +75,6 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 	w->ktBytes = 0.0;
 	w->dw.cellSize = 1.0f;
 	w->dw.invCellSize = 1.0f;
-	w->toiRan = false;
-	w->toiEventValid = false;
 	w->colorSmallPending = false;
 	w->hubSteps = 0;
 	readSwitches(w);
@@ -118,8 +116,6 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 		}
 	}
 	w->dfEpoch = 0;
-	w->toiChains = false;
-	w->toiFallbacks = 0;
 	for (int i = 0; i < 13; ++i) w->ev[i] = nullptr;
 	w->h_dstate = nullptr;
 	for (int i = 0; i < 13; ++i)
@@ -881,7 +877,7 @@ static int stepBeginImpl(b2hip_world* w, float dt, int velocity_iterations, int 
 	w->dw.stampMask = 1u << 14;
 	LAUNCH(w, k_step_begin, 1, 64, w->dw, w->gridBar.p);
 	w->restArrived = 0; // (bar[5] starts the step at 0)
-	w->toiCountersFresh = true;
+	w->toiStep.countersFresh = true;
 	rc = applyPendingFilters(w);
 	if (rc) return rc;
 	rc = applyEditOps(w, false); // (after k_step_begin: the end events of destroyed contacts belong to this step's list)

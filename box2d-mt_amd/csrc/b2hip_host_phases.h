@@ -1351,17 +1351,6 @@ static int phaseSyncFixtures(b2hip_world* w)
 	return 0;
 }
 
-// The serial event loop walks contacts by body (CSR) and searches new pairs through the hash grid.
-static int toiBuildAdjacency(b2hip_world* w, hipStream_t s)
-{
-	DW& d = w->dw;
-	LAUNCH_ON(w, s, k_toi_adj_clear, gridFor(d.nBodies + 1), 256, d);
-	LAUNCH_ON(w, s, k_toi_adj_count, gridFor(d.capContacts), 256, d);
-	deviceExclusiveScan<int>(s, d.deg, d.adjStart, d.scanTmp, w->scanCtx, w->consts.p + 4, d.nBodies + 1);
-	LAUNCH_ON(w, s, k_toi_adj_fill, gridFor(d.capContacts), 256, d);
-	return 0;
-}
-
 // Makes the hash grid reflect every proxy's fat AABB as of now, without touching the pair census (k_grid_clear): force 1
 // unless Counters::gridFresh says it already does (the TOI phase), force 2 whatever it says (the batched queries, with a
 // scan context of their own: `sf`).
@@ -1373,308 +1362,6 @@ static int gridRebuildNow(b2hip_world* w, int force, ScanFlags& sf)
 	deviceExclusiveScan<int>(w->stream, d.gridCount, d.gridStart, d.scanTmp, sf, w->consts.p + 1, (int)(d.gridMask + 1));
 	LAUNCH(w, k_grid_fill, gridFor(d.nProxies), 256, d, force);
 	return 0;
-}
-
-static int toiBuildIndexes(b2hip_world* w, bool csr, bool gridKnownFresh = false)
-{
-	DW& d = w->dw;
-	if (csr)
-	{
-		int rc = toiBuildAdjacency(w, w->stream);
-		if (rc) return rc;
-	}
-	// make the grid reflect every fat AABB as of now (the end-of-step pair update skips the rebuild when nothing
-	// moved, and TOI moves of earlier steps never enter the move buffer) - unless this step's pair update has just built it
-	// from every proxy's box and nothing moved one since (Counters::gridFresh; the kernels below check it themselves, the
-	// host saves their launches when the read-back it already has says so: 128 us of a million-proxy world's step)
-	// (a sharded rank launches them anyway: other ranks' boxes may have arrived since the host last looked - the kernels know)
-	if (gridKnownFresh && !w->spatial) return 0;
-	return gridRebuildNow(w, 1, w->scanCtx);
-}
-
-static int toiSerial(b2hip_world* w)
-{
-	DW& d = w->dw;
-	// (every caller has read this step's counters back since the pair update: phaseToiSync, the fall-backs of b2hip_step_end)
-	int rc = toiBuildIndexes(w, true, w->h_dstate->c.gridFresh != 0);
-	if (rc) return rc;
-	HIP_TRY(hipMemsetAsync(&w->d_state.p->c.toiUnsafe, 0, sizeof(int) * 3, w->stream));
-	LAUNCH(w, k_toi_loop, 1, TOI_LANES, d, w->sp);
-	if (!w->spatial) LAUNCH(w, k_toi_clear, gridFor(d.nBodies), 256, d); // (spatial worlds: k_end_step does it, behind the exchange)
-	w->toiChains = false;
-	return 0;
-}
-
-// b2World::SolveTOI (b2World.cpp:1026-1093). The first arg-min pass runs over the whole contact array; the
-// event loop only runs (one persistent workgroup) when some impact lies inside the step.
-static int phaseToiSync(b2hip_world* w);
-
-// What the component-wise event loops need besides the first pass, on the side stream beside it (see phaseToiSync).
-static inline bool toiAsideWanted(const b2hip_world* w)
-{
-	return w->toiDomainsSticky > 0 && w->toiCountersFresh && !w->spatial && w->stream2 != nullptr && !w->noSideStream && !w->debugSync && !w->debugTrace &&
-		!w->toiSnapshotTaken && !w->toiSerialOnly && !w->toiNoDomains && !listenerOn(w) && w->dw.toiEventCap == 0 && !w->dw.toiContinue;
-}
-static int toiAsideLaunch(b2hip_world* w)
-{
-	DW& d = w->dw;
-	HIP_TRY(hipEventRecord(w->evFork, w->stream));
-	HIP_TRY(hipStreamWaitEvent(w->stream2, w->evFork, 0));
-	// (the short launches first: the snapshot's bandwidth then falls into the tail of k_toi_first and the host's look at its
-	// census - beside its start it took the first pass from 120 to 220 us: loaded latency)
-	int rc = toiBuildAdjacency(w, w->stream2);
-	if (rc) return rc;
-	LAUNCH_ON(w, w->stream2, k_toi_dom_init, gridFor(d.nBodies), 256, d);
-	LAUNCH_ON(w, w->stream2, k_toi_dom_union, gridFor(d.capContacts), 256, d);
-	LAUNCH_ON(w, w->stream2, k_toi_dom_flatten, gridFor(d.nBodies), 256, d);
-	LAUNCH_ON(w, w->stream2, k_toi_snapshot, gridFor(std::max(d.nBodies, d.capContacts)), 256, d, 2);
-	HIP_TRY(hipEventRecord(w->evJoin, w->stream2));
-	return 0;
-}
-
-static inline int toiFirstGrid(b2hip_world* w);
-
-// The component path behind the first pass, its components and its snapshot: pending lists per component, the event loops, the
-// cross-component check, what has to be taken back and replayed serially. pending: the pending impacts (the host's count, or
-// its guess: every kernel strides). snapshot: 0 - taken here; 1 - taken beside the first pass, the candidates' part copied
-// here; 2 - running on the side stream, waited for here.
-static int toiDomainLaunches(b2hip_world* w, int pending, int snapshot)
-{
-	DW& d = w->dw;
-	pending = std::max(pending, 1);
-	LAUNCH(w, k_toi_dom_mark, gridFor(pending), 256, d);
-	LAUNCH(w, k_toi_dom_count, gridFor(d.capContacts), 256, d);
-	LAUNCH(w, k_toi_dom_scan, 1, 1024, d);
-	LAUNCH(w, k_toi_dom_fill, gridFor(pending), 256, d);
-	if (snapshot == 1) LAUNCH(w, k_toi_snap_cands, toiFirstGrid(w), 256, d);
-	else if (snapshot == 2) HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0));
-	else LAUNCH(w, k_toi_snapshot, gridFor(std::max(d.nBodies, d.capContacts)), 256, d, 0);
-	w->toiSnapshotTaken = true;
-	if (w->toiDomWide > 0 || w->toiDomWideOnly)
-	{
-		LAUNCH(w, k_toi_domains<TOI_LANES>, std::min(pending, 2048), TOI_LANES, d, w->sp);
-		if (w->toiDomWide > 0) w->toiDomWide -= 1;
-	}
-	else LAUNCH(w, k_toi_domains<64>, std::min(pending, 2048), 64, d, w->sp);
-	LAUNCH(w, k_toi_domains_end, std::min(pending, 1024), 256, d);
-	// components tied together by a new contact: back to the snapshot, then the serial loop over just those
-	LAUNCH(w, k_toi_dom_rollback, gridFor(std::max(std::max(d.nBodies, d.nProxies), d.capContacts)), 256, d);
-	LAUNCH(w, k_toi_loop_partial, 1, TOI_LANES, d, w->sp);
-	w->toiChainsHadGrid = true; // (the components always have it)
-	w->toiChains = true;
-	return 0;
-}
-
-// k_toi_first takes a lane per TOI candidate (grid-stride over the manager's slot table): sized from the candidate count of
-// the last read-back, generously - a wrong guess only makes the lanes loop.
-static inline int toiFirstGrid(b2hip_world* w)
-{
-	const size_t hint = (size_t)std::max(w->h_dstate->c.nToiOrder, 0);
-	return gridFor(std::min<size_t>((size_t)w->dw.capContacts, std::max<size_t>(2 * hint + 4096, 65536)));
-}
-
-// The phase without a host round trip: k_toi_first, then the chain kernels at once. Each of them leaves immediately if no
-// impact is pending (or if k_toi_first saw a bullet / kinematic partner: toiUnsafe), so the host learns the outcome from
-// the read-back b2hip_step_end makes anyway, and falls back there (snapshot restore + serial loop, or - when the pair
-// update had overflowed its optimistic small-sort path, so this phase did not see every contact - restore, finish the
-// contacts, and the synchronous phase). One read-back and ~45 us less per step with continuous physics on.
-static int phaseToi(b2hip_world* w)
-{
-	if (w->toiSerialOnly || w->toiSyncOnly || listenerOn(w) || w->dw.toiEventCap > 0 || w->dw.toiContinue || w->spatial) return phaseToiSync(w);
-	if (toiAsideWanted(w) && w->lastToiList > 0 && !w->noToiSpecDomains)
-	{
-		// The component path without the look at the first pass's census (round 5): while it has been the path of the last
-		// steps, its launches are queued behind k_toi_first at once, sized from the last step's pending count (they stride);
-		// every one of them leaves if nothing is pending. What the census would have told - the pair update unfinished, nothing
-		// pending, a capacity cut - b2hip_step_end learns from the read-back it makes anyway and settles as it does for the
-		// speculative chains; the one thing assumed - that the pair update of THIS step has left the grid fresh, as it had
-		// the step before - is checked there too (Counters::gridFresh), and a wrong guess is a serial replay from the snapshot.
-		DW& d = w->dw;
-		int rc = toiAsideLaunch(w);
-		if (rc) return rc;
-		w->toiCountersFresh = false;
-		LAUNCH(w, k_toi_first, toiFirstGrid(w), 256, d);
-		HIP_TRY(hipMemsetAsync(&w->d_state.p->c.toiUnsafe, 0, sizeof(int), w->stream)); // (k_toi_first's "not chains" bit)
-		HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0));
-		// (B2HIP_DEBUG_ASSUME_FRESH_GRID=1, for the tests: the assumption is made whatever the last step said, and the device is
-		// told the grid is stale - every such step takes the wrong-guess path of b2hip_step_end)
-		const bool assumeFresh = w->gridFreshLast || w->debugAssumeFreshGrid;
-		if (w->debugAssumeFreshGrid) HIP_TRY(hipMemsetAsync(&w->d_state.p->c.gridFresh, 0, sizeof(int), w->stream));
-		if (!assumeFresh) { rc = toiBuildIndexes(w, false, false); if (rc) return rc; }
-		rc = toiDomainLaunches(w, 2 * w->lastToiList + 256, 1);
-		if (rc) return rc;
-		// (k_toi_clear's work is done by k_end_step, which follows)
-		w->toiSpeculative = true;
-		w->toiSpecDomains = true;
-		w->toiSpecGridAssumed = assumeFresh;
-		return 0;
-	}
-	if (w->toiSyncSticky > 0)
-	{
-		// the serial loop was needed recently (bullets, kinematic partners, contact-creating events): decide from the
-		// read-back again instead of paying a wasted snapshot + state download per step
-		int rc = phaseToiSync(w);
-		if (rc) return rc;
-		if (w->h_dstate->c.nToiList == 0 || (w->toiChains && w->h_dstate->c.toiUnsafe == 0)) w->toiSyncSticky -= 1;
-		else w->toiSyncSticky = 16;
-		return 0;
-	}
-	DW& d = w->dw;
-	if (!w->toiCountersFresh)
-	{
-		HIP_TRY(hipMemsetAsync(&w->d_state.p->c.nToiList, 0, sizeof(int) * 5, w->stream));
-		HIP_TRY(hipMemsetAsync(&w->d_state.p->c.toiUnsafe, 0, sizeof(int) * 3, w->stream));
-	}
-	w->toiCountersFresh = false;
-	LAUNCH(w, k_toi_first, toiFirstGrid(w), 256, d);
-	const int haveGrid = w->toiGridSticky > 0 ? 1 : 0;
-	LAUNCH(w, k_toi_groups_begin, gridFor(std::min(d.capContacts, 1 << 16)), 256, d);
-	LAUNCH(w, k_toi_group_contacts, gridFor(std::max(d.nBodies, d.capContacts)), 256, d, 1); // (+ the snapshot)
-	w->toiSnapshotTaken = true;
-	if (haveGrid)
-	{
-		int rc = toiBuildIndexes(w, false);
-		if (rc) return rc;
-	}
-	LAUNCH(w, k_toi_chains, 1024, CHAIN_LANES, d, w->sp, haveGrid);
-	// (k_toi_clear's work is done by k_end_step, which follows)
-	w->toiChainsHadGrid = haveGrid != 0;
-	w->toiChains = true;
-	w->toiSpeculative = true;
-	return 0;
-}
-
-static int phaseToiSync(b2hip_world* w)
-{
-	DW& d = w->dw;
-	// one read-back serves both questions: did the optimistic small-sort path of the end-of-step pair update
-	// apply (else finish it first: the TOI phase must see every contact), and is any impact pending
-	int rc = 0;
-	// While the component-wise event loops have been in use (bullets: config 5), what they need besides the first pass - the
-	// snapshot (230 MB for a million bodies: bandwidth), the adjacency of all contacts and the components (a dozen short
-	// launches: latency) - does not wait for it: none of that reads what k_toi_first writes except the candidates' flags and
-	// impact times, which k_toi_snap_cands copies afterwards. It runs on the side stream (idle behind Solve) beside
-	// k_toi_first - a few heavy lanes, ~120 us - and the host's look at its census: ~180 us of the step's critical path.
-	// Void if the pair update has to be finished first (the contact array grows under it): then everything is done again below.
-	bool aside = false;
-	if (toiAsideWanted(w))
-	{
-		rc = toiAsideLaunch(w);
-		if (rc) return rc;
-		aside = true;
-	}
-	bool asideValid = aside;
-	for (int pass = 0; pass < 2; ++pass)
-	{
-		if (pass == 1 && aside)
-		{
-			// (the contact array is about to change, or has: the side stream's work is void - and must have ended)
-			HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0));
-			asideValid = false;
-		}
-		if (pass == 1 || !w->toiCountersFresh)
-		{
-			// (the first pass of a step starts from the zeros of k_step_begin)
-			HIP_TRY(hipMemsetAsync(&w->d_state.p->c.nToiList, 0, sizeof(int) * 5, w->stream));
-			HIP_TRY(hipMemsetAsync(&w->d_state.p->c.toiUnsafe, 0, sizeof(int) * 3, w->stream));
-		}
-		w->toiCountersFresh = false;
-		LAUNCH(w, k_toi_first, toiFirstGrid(w), 256, d);
-		rc = readState(w);
-		if (rc) return rc;
-		if (w->h_dstate->c.overflow & 3)
-		{
-			// the end-of-step pair update overflowed its buffer (or the contact array): grow, run the whole update again, look again
-			if (pass == 1) return setError(B2HIP_ERR_CAPACITY, "pair buffer overflow");
-			if (aside && asideValid) { HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0)); asideValid = false; }
-			rc = growPairBuffers(w);
-			if (rc) return rc;
-			rc = findNewContacts(w, true);
-			if (rc) return rc;
-			continue;
-		}
-		if (pass == 1 || w->h_dstate->c.nMoves == 0 || w->h_dstate->c.nPairs <= COUNT_RANK_MAX) break;
-		if (aside && asideValid) { HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0)); asideValid = false; }
-		rc = runSortAndCreate(w, true, w->h_dstate->c.nPairs);
-		if (rc) return rc;
-	}
-	// (whatever follows writes what the side stream reads: it has had ~200 us, the wait is a formality)
-	if (aside) HIP_TRY(hipStreamWaitEvent(w->stream, w->evJoin, 0));
-	if (w->toiDomainsSticky > 0) w->toiDomainsSticky -= 1;
-	w->last.nToiList = w->h_dstate->c.nToiList;
-	w->last.nToiCalls = w->h_dstate->c.nToiCalls;
-	w->last.nToiEvents = 0;
-	w->spContactsBeforeToi = w->h_dstate->c.nContacts;
-	w->spToiOrderBefore = w->h_dstate->c.nToiOrder;
-	// (sub-stepping: one event per call in the reference's serial order; a call that continues a step has impacts to compute
-	// even when nothing is pending yet - the event loop's first batch)
-	const bool subStepped = d.toiEventCap > 0 || d.toiContinue != 0;
-	if (w->h_dstate->c.nToiList == 0 && !d.toiContinue) return 0;
-	if (w->h_dstate->c.nToiList > d.capContacts) return setError(B2HIP_ERR_CAPACITY, "TOI list overflow");
-	w->toiRan = true;
-	if (w->h_dstate->c.toiUnsafe == 0 && !w->toiSerialOnly && !listenerOn(w) && !subStepped)
-	{
-		// every pending impact pairs a dynamic body with a static one: one wave per dynamic body, verified afterwards
-		// (b2hip_step_end falls back to the serial loop from the snapshot if a chain met a case that is order dependent)
-		// The hash grid is only needed when a chain moves a proxy out of its fat AABB: it is rebuilt while that has
-		// happened recently, otherwise such a move sends the phase to the serial loop (which rebuilds it).
-		const int groups = std::min(std::min(w->h_dstate->c.nToiList, d.nBodies), (int)TOI_GROUPS_MAX);
-		const int haveGrid = w->toiGridSticky > 0 ? 1 : 0;
-		LAUNCH(w, k_toi_groups_begin, gridFor(w->h_dstate->c.nToiList), 256, d);
-		LAUNCH(w, k_toi_group_contacts, gridFor(d.capContacts), 256, d, 0);
-		LAUNCH(w, k_toi_snapshot, gridFor(std::max(d.nBodies, d.capContacts)), 256, d, 0);
-		w->toiSnapshotTaken = true;
-		if (haveGrid)
-		{
-			rc = toiBuildIndexes(w, false, w->h_dstate->c.gridFresh != 0);
-			if (rc) return rc;
-		}
-		LAUNCH(w, k_toi_chains, std::min(groups, 1024), CHAIN_LANES, d, w->sp, haveGrid);
-		if (!w->spatial) LAUNCH(w, k_toi_clear, gridFor(d.nBodies), 256, d);
-		w->toiChainsHadGrid = haveGrid != 0;
-		w->toiChains = true;
-		return 0;
-	}
-	if (!w->toiSerialOnly && !w->toiNoDomains && !listenerOn(w) && !subStepped)
-	{
-		// bullets / kinematic partners: the event loop runs per connected component of the contact graph, side by side
-		// (b2d_kernels_toi_domains.h); b2hip_step_end falls back to the serial loop from the snapshot if a component met
-		// something that couples it to another one
-		// The snapshot (230 MB for a million bodies: bandwidth) runs on the side stream beside the dozen short launches that build
-		// the adjacency and the components (latency): nothing they write is anything it reads, the stream is drained (readState
-		// above), and the side stream is idle behind Solve. The event loops wait for it.
-		w->toiDomainsSticky = 16;
-		const bool snapAside = !asideValid && w->stream2 != nullptr && !w->noSideStream && !w->debugSync && !w->debugTrace;
-		if (snapAside)
-		{
-			LAUNCH_ON(w, w->stream2, k_toi_snapshot, gridFor(std::max(d.nBodies, d.capContacts)), 256, d, 0);
-			HIP_TRY(hipEventRecord(w->evJoin, w->stream2));
-		}
-		// (asideValid: snapshot, adjacency and components are there - the grid, if this step's pair update has not left one)
-		rc = toiBuildIndexes(w, !asideValid, w->h_dstate->c.gridFresh != 0);
-		if (rc) return rc;
-		if (!asideValid)
-		{
-			LAUNCH(w, k_toi_dom_init, gridFor(d.nBodies), 256, d);
-			LAUNCH(w, k_toi_dom_union, gridFor(d.capContacts), 256, d);
-			LAUNCH(w, k_toi_dom_flatten, gridFor(d.nBodies), 256, d);
-		}
-		HIP_TRY(hipMemsetAsync(&w->d_state.p->c.toiUnsafe, 0, sizeof(int), w->stream)); // (k_toi_first's "not chains" bit)
-		w->lastToiList = w->h_dstate->c.nToiList;
-		w->gridFreshLast = w->h_dstate->c.gridFresh != 0;
-		rc = toiDomainLaunches(w, w->h_dstate->c.nToiList, asideValid ? 1 : snapAside ? 2 : 0);
-		if (rc) return rc;
-		if (!w->spatial) LAUNCH(w, k_toi_clear, gridFor(d.nBodies), 256, d);
-		return 0;
-	}
-	if ((hasPreSolve(w) || w->spatial) && !w->toiSnapshotTaken)
-	{
-		// a PreSolve called from a sub-step may change that sub-step (toiPreSolveRounds): the phase must be able to start over
-		// (a spatially sharded world sends the other ranks what differs from this snapshot: spAfterToi)
-		LAUNCH(w, k_toi_snapshot, gridFor(std::max(d.nBodies, d.capContacts)), 256, d, 0);
-		w->toiSnapshotTaken = true;
-	}
-	return toiSerial(w);
 }
 
 // The read-back of a step (and of a between-step destroy): k_end_step writes the state rows and, behind them, the counters

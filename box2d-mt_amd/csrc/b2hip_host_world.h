@@ -97,6 +97,54 @@ struct FreeUnit
 	int leaf;
 };
 
+// The host side of b2World::SolveTOI (b2hip_host_toi.h): what it keeps on the world, sorted by what it is.
+struct ToiSwitches // read from the environment once, when the world is made (readSwitches)
+{
+	bool serialOnly = false;      // B2HIP_TOI_SERIAL: every event through the serial loop
+	bool syncOnly = false;        // B2HIP_TOI_SYNC: always look at the first pass's census before choosing a path (phaseToiSync)
+	bool noDomains = false;       // B2HIP_TOI_NO_DOMAINS: bullets / kinematic partners through the serial loop only
+	bool noSpecDomains = false;   // B2HIP_TOI_NO_SPEC_DOMAINS=1: the component path always looks at the census first
+	bool domWideOnly = false;     // B2HIP_TOI_DOM_WIDE=1: the components' event loops always get 512 lanes (comparison)
+	bool assumeFreshGrid = false; // B2HIP_DEBUG_ASSUME_FRESH_GRID=1 (tests: the speculative component path's wrong-guess handling)
+	bool why = false;             // B2HIP_TOI_WHY: why a parallel TOI path handed the phase to the serial loop, on stderr
+};
+struct ToiHints // what one step's phase leaves for the next ones: hysteresis and guesses
+{
+	int syncSticky = 0;         // steps for which the phase decides from a read-back again (see phaseToi)
+	int gridSticky = 0;         // steps for which the TOI chains still get a rebuilt hash grid
+	int domainsSticky = 0;      // steps for which the component-wise event loops' preparations start beside k_toi_first (phaseToiSync)
+	int domWide = 0;            // steps for which the components' event loops get 512 lanes again (one of them met more candidate contacts than a wave has lanes)
+	int lastToiList = 0;        // pending impacts of the last step that took the component path (sizes the speculative launches)
+	bool gridFreshLast = false; // ... and whether its pair update had left the grid fresh (what the speculative flow assumes of the next)
+	bool eventValid = false;    // b2hip_solve_toi has run in this world: phase stamp 12 is there (b2Profile::solveTOI)
+};
+// What this step's phase has done so far. Its flags are cleared by begin() and dropVerdict() alone; dropVerdict() is called by
+// toiRunAgain (a second run starts), toiSettle (a queued path found nothing pending) and spAfterToi (a sharded rank is done).
+struct ToiStep
+{
+	enum Path { None, Chains, Components, Serial }; // whose result stands: the chains' and the components' is a verdict still out
+	Path path = None;             // (Counters::toiUnsafe, read back at the end of the step or carried by a sharded rank's header)
+	bool ran = false;             // impacts were pending: the step's TOI counters are reported (b2hip_get_counters)
+	bool speculative = false;     // the path was queued without the first pass's census (phaseToi): the end of the step reads what it would have said
+	bool chainsHadGrid = false;   // path == Chains: they ran with the hash grid. Stored: toiSettle updates ToiHints::gridSticky, which decided it, before it asks
+	bool specGridAssumed = false; // speculative components: queued on the guess of a fresh grid. Stored: the guess came from a hint and a switch
+	bool snapshotTaken = false;   // the phase saved the state it started from; stays up through every second run, which goes back to the same state
+	bool countersFresh = false;   // the device's TOI counters are still the zeros of k_step_begin (set there, not by begin())
+	std::vector<int4> verdicts;   // this step's PreSolve answers per TOI log slot (the device's copy: DW::toiVerdict)
+
+	bool verdictPending() const { return path == Chains || path == Components; }
+	bool specComponents() const { return speculative && path == Components; } // the component path queued without its census
+	bool hadGrid() const { return path == Components || (path == Chains && chainsHadGrid); } // (the components always have it)
+	void dropVerdict() { path = None; speculative = false; }
+	void begin() { dropVerdict(); ran = snapshotTaken = false; verdicts.clear(); } // a step's phase starts (solveToiImpl)
+};
+struct ToiStats // since the world was created; n[] in the order b2hip_debug_read 25 reports and documents it
+{
+	enum { ChainsQueued, ChainsCensus, ComponentsQueued, ComponentsCensus, SerialDirect, RedoLatePairs, GridRetry, SerialFallback, OverflowRerun, PreSolveRerun, N };
+	long long n[N] = {};
+	long long chainContacts = 0; // contacts created by the close-out of the parallel TOI chains
+};
+
 struct b2hip_world
 {
 	b2hip_world_def def;
@@ -350,7 +398,6 @@ struct b2hip_world
 	bool traceLaunches = false;  // B2HIP_TRACE_LAUNCHES=1 (with B2HIP_DEBUG): every kernel's name before the stream is drained behind it
 	bool tracePartition = false; // B2HIP_TRACE_PARTITION=1: why a partition was made, on stderr
 	bool traceRecovery = false;  // B2HIP_TRACE_RECOVERY=1: every recovery, on stderr
-	bool toiWhy = false;         // B2HIP_TOI_WHY: why a parallel TOI path handed the phase to the serial loop, on stderr
 	bool handoverWhy = false;    // B2HIP_HANDOVER_WHY: the post mortem of a timed-out wait inside a block solver, on stderr
 	bool shardTrace = false;     // B2HIP_SHARD_TRACE=1: the size of every all-gather of a spatially sharded world (rank 0), on stderr
 	double stepDeadlineS = 300.0; // B2HIP_STEP_DEADLINE_S: a poll of the host gives up on a stream that stays busy this long
@@ -358,9 +405,6 @@ struct b2hip_world
 	bool gridHalf = false;       // the hash grid's cell is half the limit: chosen from the candidates per moved proxy of the last pair update
 	bool gridForced = false;     // B2HIP_GRID_HALF=0 / 1 fixes it
 	int pairsLargeSticky = 0;    // steps for which the pair update still reads its pair count back before it sorts
-	int toiPreSolveReruns = 0; // runs of the TOI phase repeated because a PreSolve changed its contact inside a sub-step
-	int toiGridRetries = 0;      // steps whose chains were run again with the hash grid instead of serially
-	int toiChainContacts = 0;    // contacts created by the close-out of the parallel TOI chains since the world was made
 	int recolorCountdown = 0;    // ... and steps until such islands are coloured afresh (phaseSolve)
 	bool blocksTooBig = false;   // the large islands hold more constraints than any block solver takes: no partition (phaseSolve)
 	bool noSweepBlocks = false;  // B2HIP_NO_SWEEP_BLOCKS=1: jointed / hub islands stay on the launch-per-colour kernels
@@ -414,27 +458,17 @@ struct b2hip_world
 	size_t pairCapHint = 0; // pair-buffer size asked for after an overflow (growPairBuffers)
 	int constsUploaded[2] = { -1, -1 };
 	int* constsUploadedAt = nullptr;
-	int toiSyncSticky = 0; // steps for which the TOI phase decides from a read-back again (see phaseToi)
-	int toiGridSticky = 0; // steps for which the TOI chains still get a rebuilt hash grid
-	int lastToiList = 0;      // pending impacts of the last step that took the component path (sizes the speculative launches)
-	bool gridFreshLast = false; // ... and whether its pair update had left the grid fresh (what the speculative flow assumes of the next)
-	bool toiSpecDomains = false, toiSpecGridAssumed = false; // this step's TOI phase was queued without the census (phaseToi) / assuming a fresh grid
-	bool debugAssumeFreshGrid = false; // B2HIP_DEBUG_ASSUME_FRESH_GRID=1 (tests: the speculative component path's wrong-guess handling)
-	bool noToiSpecDomains = false; // B2HIP_TOI_NO_SPEC_DOMAINS=1: always look at the census first (phaseToiSync)
-	int toiDomWide = 0;       // steps for which the components' event loops get 512 lanes again (one of them met more candidate contacts than a wave has lanes)
-	bool toiDomWideOnly = false; // B2HIP_TOI_DOM_WIDE=1: always (comparison)
-	int toiDomainsSticky = 0; // steps for which the component-wise event loops' preparations start beside k_toi_first (phaseToiSync)
-	bool toiChainsHadGrid = false; // the chains of this step ran with the grid (else a moved proxy is all "unsafe" means)
-	bool toiSnapshotTaken = false; // this step's TOI phase saved the state it started from (k_toi_snapshot)
-	std::vector<int4> toiVerdicts; // this step's PreSolve answers per TOI log slot (the device's copy: DW::toiVerdict)
+	// the host side of b2World::SolveTOI (b2hip_host_toi.h), by what kind of thing it is
+	ToiSwitches toiSw;
+	ToiHints toiHints;
+	ToiStep toiStep;
+	ToiStats toiStats;
 	// b2World::SetSubStepping (b2World.h:183; b2World.cpp:1082-1086, 1668): with the flag on a step call solves one TOI event
 	// and leaves the step open; the calls that follow run Collide and the next event but no island solve, until no event is left
 	bool stepComplete = true;  // b2World::m_stepComplete
 	bool stepSolves = true;    // this call runs Solve (it started from a complete step)
-	bool toiCountersFresh = false, toiSpeculative = false, toiSyncOnly = false, toiNoDomains = false;
-	bool toiRan, toiEventValid, toiChains, toiSerialOnly, kernelTimingLaunches, colorSmallPending;
+	bool kernelTimingLaunches, colorSmallPending;
 	int hubSteps;
-	int toiFallbacks;                                  // steps whose TOI chains had to be redone serially
 	bool debugTrace;                                   // B2HIP_TRACE=1: hash the body state after every solver stage
 	std::vector<std::pair<std::string, uint64_t> > trace;
 	DevArray<float4> dbgPreVel, dbgVel;
@@ -719,6 +753,21 @@ static inline bool hasPreSolve(const b2hip_world* w) { return w->preSolveFn != n
 // any listener callback switched on: the TOI sub-steps log their calls (b2hip_get_toi_callbacks) and run in serial order
 static inline bool listenerOn(const b2hip_world* w) { return w->eventsOn || hasPreSolve(w) || w->postSolveOn; }
 
+// a manifold as the listener records carry it (PreSolveRec, ToiLogRec), for the callbacks
+static void toManifold(b2hip_manifold* m, float4 m0, float4 m1, float4 imp, int4 m3)
+{
+	m->type = m3.z;
+	m->point_count = m3.w;
+	m->local_normal[0] = m0.x; m->local_normal[1] = m0.y;
+	m->local_point[0] = m0.z; m->local_point[1] = m0.w;
+	m->point_local[0][0] = m1.x; m->point_local[0][1] = m1.y;
+	m->point_local[1][0] = m1.z; m->point_local[1][1] = m1.w;
+	m->normal_impulse[0] = imp.x; m->tangent_impulse[0] = imp.y;
+	m->normal_impulse[1] = imp.z; m->tangent_impulse[1] = imp.w;
+	m->id_key[0] = (uint32_t)m3.x;
+	m->id_key[1] = (uint32_t)m3.y;
+}
+
 static int ktRecord(b2hip_world* w)
 {
 	if (!w->kernelTiming) return 0;
@@ -845,13 +894,13 @@ static void readSwitches(b2hip_world* w)
 	w->noBlocks = envSet("B2HIP_NO_BLOCKS"); // no block partition at all (colours as before it existed)
 	w->blockLanes = 0; // chosen per partition (see phaseSolve); B2HIP_BLOCK_LANES = 256 | 512 | 1024 forces one size
 	if (const char* e = getenv("B2HIP_BLOCK_LANES")) w->blockLanes = atoi(e) == 512 ? 512 : (atoi(e) == 256 ? 256 : (atoi(e) == 1024 ? 1024 : 0));
-	w->toiSerialOnly = envSet("B2HIP_TOI_SERIAL");
-	w->toiSyncOnly = envSet("B2HIP_TOI_SYNC");
-	w->toiDomWideOnly = envSet("B2HIP_TOI_DOM_WIDE");
-	w->noToiSpecDomains = envSet("B2HIP_TOI_NO_SPEC_DOMAINS");
-	w->debugAssumeFreshGrid = envSet("B2HIP_DEBUG_ASSUME_FRESH_GRID");
-	w->toiNoDomains = envSet("B2HIP_TOI_NO_DOMAINS"); // bullets / kinematic partners through the serial loop only
-	w->toiWhy = envSet("B2HIP_TOI_WHY");
+	w->toiSw.serialOnly = envSet("B2HIP_TOI_SERIAL");
+	w->toiSw.syncOnly = envSet("B2HIP_TOI_SYNC");
+	w->toiSw.domWideOnly = envSet("B2HIP_TOI_DOM_WIDE");
+	w->toiSw.noSpecDomains = envSet("B2HIP_TOI_NO_SPEC_DOMAINS");
+	w->toiSw.assumeFreshGrid = envSet("B2HIP_DEBUG_ASSUME_FRESH_GRID");
+	w->toiSw.noDomains = envSet("B2HIP_TOI_NO_DOMAINS");
+	w->toiSw.why = envSet("B2HIP_TOI_WHY");
 	w->handoverWhy = envSet("B2HIP_HANDOVER_WHY");
 	w->shardTrace = envOn("B2HIP_SHARD_TRACE");
 	w->recoverOn = !envOn("B2HIP_NO_RECOVER");
@@ -1095,7 +1144,7 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 	d.toiLog = listenerOn(w) && w->def.continuous ? w->toiLog.p : nullptr;
 	d.capToiLog = (int)std::min<size_t>(w->toiLog.cap, 0x7fffff);
 	d.toiVerdict = hasPreSolve(w) && w->def.continuous ? w->toiVerdict.p : nullptr;
-	d.nToiVerdict = std::min((int)w->toiVerdicts.size(), (int)std::min<size_t>(w->toiVerdict.cap, 0x7fffff));
+	d.nToiVerdict = std::min((int)w->toiStep.verdicts.size(), (int)std::min<size_t>(w->toiVerdict.cap, 0x7fffff));
 	return 0;
 }
 
