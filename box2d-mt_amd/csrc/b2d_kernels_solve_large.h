@@ -199,7 +199,6 @@ __global__ __launch_bounds__(256) void k_color_check(DW W)
 	// is cut, every one is an "orphan". Said once here instead of found out by three or four gathers per body and constraint.
 	const bool noPart = S->c.nBlocks == 0;
 	auto isCut = [&](int bodyA, bool nsA, int bodyB, bool nsB) -> bool { return noPart ? false : constraintIsCut(W, bodyA, nsA, bodyB, nsB); };
-	int bad = 0;
 	int uncolored = 0;
 	int maxColor = 0;
 	int orphanRows = 0, cutRows = 0;
@@ -334,9 +333,9 @@ __global__ __launch_bounds__(256) void k_color_check(DW W)
 			if (u < COLOR_SMALL_MAX) W.compactList[u] = s;
 		}
 	}
-	// needRecolor bit0: two constraints on one body share a colour -> colour everything again;
-	// nUncolored: constraints without a colour yet -> incremental rounds on top of the existing masks
-	if (bad) atomicOr(&S->c.needRecolor, 1);
+	// (two constraints on one body that share a colour - Counters::needRecolor, colour everything again - are found by
+	// k_color_masks, the kernel behind this one, body by body; this kernel only counts the constraints without a colour:
+	// incremental rounds on top of the existing masks)
 	// (nUncolored = nUncolList - the same rows, counted once, by the workgroups' list allocations above; k_color_masks, the
 	// kernel behind this one, copies it. A sum per wave on top was 1 500 more atomics on the line of Counters that every
 	// workgroup of this kernel already queues at: a clock around the sections showed 13 - 45 us per workgroup spent there)

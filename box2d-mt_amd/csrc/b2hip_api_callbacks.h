@@ -195,6 +195,22 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 //     [2] components queued without it, [3] components after it, [4] the serial loop chosen from it (second runs count under
 //     [1], [3], [4] again). Rungs of the fall-back ladder: [5] redo behind a late pair sort, [6] chains again with the hash grid,
 //     [7] serial replay (toi_serial_fallbacks), [8] re-run after a full contact array, [9] PreSolve re-run (toi_pre_solve_reruns).
+// 12 - 21, 26 - 28: the plan of the large-island solve, read by tests/plan_ref.py (its docstring says from which launch to which
+//     each array holds the step's plan). 12 the colour census (ints, [0, 65)), 13 bodyColorMask, 14 deg, 15 hubList, 16 bodyActive,
+//     17 b_blk1, 18 li_ref (int4 per row), 19 rowColor, 20 blkRowStart, 21 bodyRest: raw device arrays, `count` elements from `first`.
+// 26: the effective block (+ 1, 0 = none) of `count` bodies from `first`, ints: what effBlk (b2d_kernels_island.h) returns,
+//     evaluated on the host from copies of b_blk1, b_adopt, b_flags and the device's counters. Launches nothing.
+// 27: the last pass of the large-island solve as the host planned it (LargePass, b2hip_host_phases.h) and the counters that
+//     belong to it, `count` (<= 28) ints from `first`: [0] passes run since the world was created, [1] solver (0 a launch per
+//     colour, 1 k_solve_blocks, 2 k_blocks_sweep, 3 exact order, -1 none yet), [2] the safe pass behind a recovery, [3] restFirst
+//     (0x7fffffff: no rest colours), [4] tailFirst, [5] bigEnd, [6] useRest, [7] fuseHub, [8] blockSort, [9] hubWide,
+//     [10] serialOrphans, [11] colours the pass sweeps, [12] hasHubs, [13] hasJoints, [14] hub list by k_hub_build, [15] sweeps
+//     end in k_sweep_end / k_rest_hub, [16] leftover hub rows go to k_large_hub; from the device's counters as they stand now:
+//     [17] nHubRows, [18] nHubWide, [19] the primary hub's body id (hubMeta[0]; -1: no hub), [20] its degree, [21] nBlocks,
+//     [22] nColors, [23] maxDegree; switches: [24] B2HIP_FORCE_LARGE, [25] smallMaxW, [26] B2HIP_TEST_MAX_COLORS, [27] joints
+//     created so far (destroyed ones included: the range of id 28).
+// 28: the bodies of `count` joints from `first`, four ints each: bodyA, bodyB (-1, -1: destroyed), a gear joint's bodyC, bodyD
+//     (else -1, -1). From the host's mirror.
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -263,6 +279,67 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 	{
 		if (first < 0 || count < 0 || first + count > ToiStats::N) return setError(B2HIP_ERR_INVALID, "TOI host statistics: [0, 10)");
 		memcpy(out, w->toiStats.n + first, (size_t)count * sizeof(long long));
+		return 0;
+	}
+	case 26:
+	{
+		// (effBlk, b2d_kernels_island.h, evaluated here from copies of what it reads; ownIdBlock is the device's own function)
+		const int nb = (int)std::min(w->bodies.size(), w->upBodies); // (the bodies the device has rows for)
+		if (first < 0 || count < 0 || first + count > nb) return setError(B2HIP_ERR_INVALID, "effective blocks: [0, uploaded bodies)");
+		if (count == 0) return 0;
+		if (!w->d_state.p || !w->b_blk1.p || !w->b_adopt.p || !w->b_flags.p) return setError(B2HIP_ERR_INVALID, "effective blocks: nothing uploaded yet");
+		Counters c;
+		HIP_TRY(hipMemcpy(&c, &w->d_state.p->c, sizeof(Counters), hipMemcpyDeviceToHost));
+		std::vector<int> blk1((size_t)count), adopt((size_t)count);
+		std::vector<uint32_t> flags((size_t)count);
+		HIP_TRY(hipMemcpy(blk1.data(), w->b_blk1.p + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(adopt.data(), w->b_adopt.p + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(flags.data(), w->b_flags.p + first, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		const int blocks = c.nBlocks < MAX_BLOCKS ? c.nBlocks : MAX_BLOCKS;
+		const bool ownIdOff = (w->dw.nJoints != 0 || c.maxDegree > HUB_DEGREE) && w->dw.noOwnIdBlocks >= 0;
+		int* e = (int*)out;
+		for (int k = 0; k < count; ++k)
+		{
+			const int offered = adopt[k] & 0x7ff; // (adoptBlock)
+			if (blk1[k]) e[k] = blk1[k];
+			else if (offered || w->dw.noOwnIdBlocks > 0) e[k] = offered;
+			else if ((flags[k] & BF_LARGE) == 0 || ownIdOff) e[k] = 0;
+			else e[k] = blocks > 0 ? ownIdBlock(first + k, blocks) : 0;
+		}
+		return 0;
+	}
+	case 27:
+	{
+		const int N = 28;
+		if (first < 0 || count < 0 || first + count > N) return setError(B2HIP_ERR_INVALID, "large-island plan: [0, 28)");
+		const b2hip_world::PlanRecord& r = w->planRecord;
+		Counters c;
+		memset(&c, 0, sizeof(c));
+		unsigned long long meta = 0ull;
+		if (w->d_state.p) HIP_TRY(hipMemcpy(&c, &w->d_state.p->c, sizeof(Counters), hipMemcpyDeviceToHost));
+		if (w->hubMeta.p) HIP_TRY(hipMemcpy(&meta, w->hubMeta.p, sizeof(meta), hipMemcpyDeviceToHost));
+		const int v[N] = { (int)(r.passes & 0x7fffffff), r.solver, r.safe, r.restFirst, r.tailFirst, r.bigEnd, r.useRest, r.fuseHub, r.blockSort, r.hubWide,
+			r.serialOrphans, r.nColors, r.hasHubs, r.hasJoints, r.hubBuildOne, r.useSweepEnd, r.leftoverApart,
+			c.nHubRows, c.nHubWide, meta != 0ull ? (int)(uint32_t)(meta & 0xffffffffull) : -1, (int)(meta >> 32),
+			c.nBlocks, c.nColors, c.maxDegree, w->forceLarge, w->dw.smallMaxW, w->dw.testMaxColors, (int)w->joints.size() };
+		memcpy(out, v + first, (size_t)count * sizeof(int));
+		return 0;
+	}
+	case 28:
+	{
+		const int nj = (int)w->joints.size();
+		if (first < 0 || count < 0 || first + count > nj) return setError(B2HIP_ERR_INVALID, "joint bodies: [0, joints)");
+		int* q = (int*)out;
+		for (int k = 0; k < count; ++k)
+		{
+			const RevoluteJoint& j = w->joints[(size_t)(first + k)];
+			const bool dead = j.type == B2D_JOINT_DEAD;
+			const bool gear = j.type == B2D_JOINT_GEAR && j.enableLimit >= 0 && (size_t)j.enableLimit < w->gears.size();
+			q[4 * k + 0] = dead ? -1 : j.bodyA;
+			q[4 * k + 1] = dead ? -1 : j.bodyB;
+			q[4 * k + 2] = gear ? w->gears[(size_t)j.enableLimit].bodyC : -1;
+			q[4 * k + 3] = gear ? w->gears[(size_t)j.enableLimit].bodyD : -1;
+		}
 		return 0;
 	}
 	default: return setError(B2HIP_ERR_INVALID, "bad array id");

@@ -883,7 +883,14 @@ static LargePlan planLargePass(const b2hip_world* w, const SolveStep& s, const b
 	p.useRest = p.useSweepEnd && p.restFirst < nColors;
 	// (round 6: one single-workgroup launch sorts the hub group's segment of the row array in place - k_hub_build - where the
 	// last step's list was short enough for its keys to sit in LDS; the four launches of layoutRows otherwise)
-	p.hubBuildOne = s.hasHubs && !w->noHubBuild && w->last.nHubRows <= HUB_BUILD_LDS;
+	// (... and on a step with constraints that found no colour free, however long the list: k_hub_flag hands the scan TWO counts
+	// in one int - the rows of the fixed point below bit 20, everything else above it - so k_hub_fill places at most 2 047 rows
+	// behind the wide ones; orphans are held below that by repartition()'s misfit, rows without a colour are not.
+	// tests/test_gpu_large_plan.py, Tumbler 60 with two colours per range: 4 370 of them. k_hub_build has no such limit.
+	// With the fixed point on, the rows of every hub but the primary one are behind the wide ones too: a world that had more than
+	// 1 024 such rows in the last step - the census still carries its counts - stays with k_hub_build as well.)
+	const bool manyBehindWide = d.hubWide && c.nHubRows - c.nHubWide > 1024;
+	p.hubBuildOne = s.hasHubs && !w->noHubBuild && (w->last.nHubRows <= HUB_BUILD_LDS || s.colorSpill || manyBehindWide);
 	p.gK = gridFor(std::max(s.nLContacts / std::max(nColors, 1), 1) * 2);
 	// A colour launch is a chain of dependent loads per lane (~4.5 us whatever it holds): a lane that makes a second trip
 	// of the grid-stride loop pays the chain twice - the Tumbler's five biggest colours (41 000 - 42 000 rows against a grid
@@ -1193,8 +1200,23 @@ struct LargePass
 		return endOfSweep(2, it);
 	}
 
+	// (for b2hip_debug_read 27: what this pass was planned as)
+	void recordPlan() const
+	{
+		b2hip_world::PlanRecord& r = w->planRecord;
+		r.passes += 1;
+		r.solver = s.exactLarge ? 3 : (s.useBlocks ? 1 : (s.useSweep ? 2 : 0));
+		r.safe = p.safe ? 1 : 0;
+		r.restFirst = p.restFirst; r.tailFirst = p.tailFirst; r.bigEnd = p.bigEnd;
+		r.useRest = p.useRest ? 1 : 0; r.fuseHub = p.fuseHub ? 1 : 0;
+		r.blockSort = d.blockSort; r.hubWide = d.hubWide; r.serialOrphans = d.serialOrphans;
+		r.nColors = s.nColors; r.hasHubs = s.hasHubs ? 1 : 0; r.hasJoints = s.hasJoints ? 1 : 0;
+		r.hubBuildOne = p.hubBuildOne ? 1 : 0; r.useSweepEnd = p.useSweepEnd ? 1 : 0; r.leftoverApart = p.leftoverApart ? 1 : 0;
+	}
+
 	int run()
 	{
+		recordPlan();
 		int rc = layoutRows();
 		if (rc) return rc;
 		stampPhase(w, 7);
@@ -1265,6 +1287,19 @@ static int solveLargeIslands(b2hip_world* w, SolveStep& s)
 	chooseLargeSolver(w, s);
 	if (int rc = colorLargeIslands(w, s)) return rc;
 	if (s.colorSpill) w->colorRecoveries += 1;
+	// A constraint that found no colour free joined the hub group AFTER k_color_check had counted it among its home block's
+	// rows (Counters / blkRowStart): laid out by block it would leave its block's segment one row short - a stale row there,
+	// which k_blocks_sweep / k_solve_blocks would solve - and push the hub group's segment past the last row k_large_init
+	// fills (found by tests/test_gpu_large_plan.py: Tumbler 60 with two colours per range; the 31 cut colours can run out without
+	// any switch, on two bodies with 31 other cut constraints between them). Such a step lays its rows out by colour - k_color_scan takes the
+	// groups from the counts as they stand now - and runs launch per colour, like the second pass of a recovered step.
+	if (s.colorSpill && (s.useBlocks || s.useSweep))
+	{
+		if (w->traceRecovery) fprintf(stderr, "[b2hip] a constraint without a free colour is swept with the hub rows: rows by colour, a launch per colour this step\n");
+		s.useBlocks = s.useSweep = false;
+		s.colorsOnDevice = false;
+		w->dw.blockSort = 0;
+	}
 	// (a constraint without a colour carries HUB_COLOR: the colours to launch end below it)
 	if (!s.exactLarge && s.nColors > HUB_COLOR) s.nColors = HUB_COLOR;
 	LargePass pass(w, s, false);

@@ -413,6 +413,15 @@ struct b2hip_world
 	int blockLanes = 0;          // forced workgroup size of k_solve_blocks (B2HIP_BLOCK_LANES), 0 = chosen per partition
 	bool noBlocks = false;       // B2HIP_NO_BLOCKS=1: no block partition (large islands through the launch-per-colour kernels)
 	int blockSteps = 0;          // steps solved by k_solve_blocks (diagnostics)
+	// What the last pass of the large-island solve decided before its first launch (LargePass: its LargePlan and the solver
+	// choice it ran under), kept for b2hip_debug_read 27 - tests/plan_ref.py checks the device's tables against it.
+	struct PlanRecord
+	{
+		long long passes = 0;      // passes run since the world was created (a recovered step runs two)
+		int solver = -1;           // 0 a launch per colour, 1 k_solve_blocks, 2 k_blocks_sweep, 3 exact order (levels as colours); -1 none yet
+		int safe = 0, restFirst = 0x7fffffff, tailFirst = 0, bigEnd = 0, useRest = 0, fuseHub = 0, blockSort = 0, hubWide = 0, serialOrphans = 0;
+		int nColors = 0, hasHubs = 0, hasJoints = 0, hubBuildOne = 0, useSweepEnd = 0, leftoverApart = 0;
+	} planRecord;
 
 	// pinned host buffers
 	float* h_state;             // pinned, coherent: k_end_step writes the read-back into it (d_hstate = its device address)
