@@ -231,6 +231,7 @@ void b2hip_world_destroy(b2hip_world* w)
 	w->qIn.release(); w->qCounts.release(); w->qOffsets.release(); w->qItems.release(); w->qFlags.release(); w->qScanWork.release();
 	w->qScanWords.release(); w->qWords.release(); w->qHits.release(); w->qDistances.release(); w->qPoses.release(); w->qShapes.release();
 	w->qKeys.release(); w->qKeysWork.release(); w->qAny.release();
+	w->bcSlot.release(); w->bcIds.release(); w->bcCounts.release(); w->bcRecords.release(); w->bcTotals.release();
 	if (w->qPinned) (void)hipHostFree(w->qPinned);
 	if (w->h_state) (void)hipHostFree(w->h_state);
 	if (w->h_dstate) (void)hipHostFree(w->h_dstate);

@@ -250,6 +250,14 @@ struct b2hip_world
 	DevArray<uint8_t> qAny;                  // b2hip_ray_cast_any
 	DevArray<QueryPose> qPoses; // shape queries and casts: pose, shape index, translation per query
 	DevArray<ShapeRec> qShapes; // ... and the call's query shapes (the GJK proxies point into this table)
+	// per-body contact lists and totals (b2hip_api_body_contacts.h): body -> slot in the batch (-1: not asked for), the batch's
+	// ids, two counters per slot ([0, n]: every contact, [n + 1, 2n + 1]: the touching ones), the records; the lists themselves
+	// share qOffsets / qItems / qFlags and the scan scratch with the queries. bcSeen / bcEpoch: the host's duplicate check.
+	DevArray<int> bcSlot, bcIds, bcCounts;
+	DevArray<b2hip_body_contact> bcRecords;
+	DevArray<b2hip_body_contact_total> bcTotals;
+	std::vector<uint32_t> bcSeen;
+	uint32_t bcEpoch = 0;
 	ScanFlags qScan;
 	void* qPinned = nullptr;
 	size_t qPinnedBytes = 0;

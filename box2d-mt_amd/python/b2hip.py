@@ -139,6 +139,10 @@ SHAPE_CAST_DTYPE = np.dtype([("shape", "i4"), ("x", "f4"), ("y", "f4"), ("angle"
 SHAPE_RANGE_DTYPE = np.dtype([("shape", "i4"), ("x", "f4"), ("y", "f4"), ("angle", "f4"), ("max_distance", "f4"), ("pad", "i4")])
 DISTANCE_HIT_DTYPE = np.dtype([("fixture", "i4"), ("body", "i4"), ("point_a", "f4", 2), ("point_b", "f4", 2), ("distance", "f4"),
                                ("iterations", "i4")])
+BODY_CONTACT_DTYPE = np.dtype([("contact_index", "i4"), ("other_body", "i4"), ("fixture", "i4"), ("other_fixture", "i4"),
+                               ("normal", "f4", 2), ("normal_impulse", "f4"), ("tangent_impulse", "f4")])
+BODY_CONTACT_TOTAL_DTYPE = np.dtype([("contacts", "i4"), ("touching", "i4"), ("impulse", "f4", 2), ("normal_impulse", "f4"),
+                                     ("max_normal_impulse", "f4"), ("points", "i4"), ("pad", "i4")])
 
 _lib = None
 
@@ -215,6 +219,8 @@ def _configure(L, optional_ok=False):
                                          C.c_void_p],
         "b2hip_query_shapes_within": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(QueryFilter), C.c_int,
                                       C.c_void_p, C.c_void_p],
+        "b2hip_body_contacts": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_body_contact_totals": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     }
     for name, argtypes in sigs.items():
         try:
@@ -707,6 +713,38 @@ class World:
         r, ns, table = self._ranges(shapes, poses, max_distance, shape_index)
         return self._query(self.L.b2hip_query_shapes_within, r, len(r), mask, sensors, lead=(ns, C.cast(table, C.c_void_p)),
                            dtype=DISTANCE_HIT_DTYPE)
+
+    # ---- per-body contact lists and totals on the device (include/b2hip.h: b2hip_body_contacts, b2hip_body_contact_totals)
+    @staticmethod
+    def _body_ids(bodies):
+        b = np.ascontiguousarray(bodies, np.int32)
+        if b.ndim != 1:
+            raise ValueError("bodies: an (n,) array of body ids is expected, got shape %s" % (b.shape,))
+        return b
+
+    def body_contacts(self, bodies, touching_only=True):
+        """The contacts of each body of `bodies` (ids, each once): (offsets[n + 1], records) with
+        records[offsets[i]:offsets[i + 1]] the BODY_CONTACT_DTYPE records of bodies[i] in ascending contact_index (an index into
+        contacts() read at the same point); normal points from the other body towards this one."""
+        b = self._body_ids(bodies)
+        n = len(b)
+        offsets = np.zeros(n + 1, np.int32)
+        records = np.zeros(max(n, 1) * 8, BODY_CONTACT_DTYPE)
+        for _ in range(2):  # (once more with the exact capacity when the first guess was short)
+            total = _check(self.L.b2hip_body_contacts(self.p, n, b.ctypes.data_as(C.c_void_p), int(bool(touching_only)), records.size,
+                                                      offsets.ctypes.data_as(C.c_void_p), records.ctypes.data_as(C.c_void_p)))
+            if total <= records.size:
+                return offsets, records[:total]
+            records = np.zeros(total, BODY_CONTACT_DTYPE)
+        raise B2HipError("body_contacts: the result grew between two identical calls")
+
+    def body_contact_totals(self, bodies):
+        """One BODY_CONTACT_TOTAL_DTYPE record per body of `bodies`: its contacts, how many touch, and over the touching ones
+        the net impulse of the last step on the body (world frame), the sum and the largest of the normal impulses, the points."""
+        b = self._body_ids(bodies)
+        out = np.zeros(len(b), BODY_CONTACT_TOTAL_DTYPE)
+        _check(self.L.b2hip_body_contact_totals(self.p, len(b), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def solver_timing(self):
         ms, by, ct, b = C.c_float(), C.c_double(), C.c_int(), C.c_int()

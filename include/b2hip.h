@@ -926,6 +926,73 @@ int b2hip_ray_cast_all(b2hip_world* w, int n, const float* rays4n, const b2hip_q
                        b2hip_ray_hit* hits);
 int b2hip_ray_cast_any(b2hip_world* w, int n, const float* rays4n, const b2hip_query_filter* f, uint8_t* out);
 
+/* ---- Batched per-body contact lists and contact totals on the device (csrc/b2hip_api_body_contacts.h,
+ * csrc/b2d_kernels_body_contacts.h) -------------------------------------------------------------------------------------------
+ * What touches each of my bodies, and how hard: the touch sensor, the foot contact, the force sensor of many agents, in one
+ * blocking call between steps, without copying the world's contacts (96 bytes each) to the host. Both calls only read: a
+ * world on which they are used steps bit for bit like one on which they are not, and the same call gives the same bytes run
+ * after run.
+ *
+ * bodies: n body ids, each in [0, b2hip_body_count) and each at most once.
+ * The list of body b: every contact k of b2hip_get_contacts, as that call would answer at the same moment, with
+ *   body_a == b || body_b == b; with touching_only != 0 only those with flags & 1. Each appears once, in ascending
+ *   contact_index. A contact between two bodies of the batch appears in both lists. A destroyed body has an empty list.
+ * Edits made since the last step are seen as b2hip_get_contacts / b2hip_get_body_states see them: the host mirror is uploaded
+ *   and the queued contact-array operations are applied first, so the contacts of a body destroyed since the step are gone,
+ *   contact_index agrees with b2hip_get_contacts called next, and a transform set since the step is the one the normals use.
+ * Record (b2hip_body_contact): fixture is this body's fixture id and other_fixture the other body's (a chain's child is a
+ *   fixture id of its own, as in b2hip_contact).
+ *   normal: b2WorldManifold::Initialize's normal for the contact's manifold and the two bodies' current transforms (the
+ *   points are not computed, so no radii enter), with the sign + when this body is body_b and - when it is body_a: it
+ *   points from the other body towards this one. b2ContactSolver applies P = jn n + jt cross(n, 1) as -P to A and +P to B,
+ *   so with this orientation the impulse on THIS body is normal_impulse * normal + tangent_impulse * (normal.y, -normal.x)
+ *   on either side.
+ *   normal_impulse / tangent_impulse: the sum over the manifold points j < point_count - a one-point contact's is that
+ *   point's, a two-point contact's is imp0 + imp1 (one fp32 add). A contact with point_count == 0 (a sensor overlap, a
+ *   contact that is not touching) has normal = (0, 0) and zero impulses.
+ * b2hip_body_contacts: offsets (n + 1) are always complete, records receives the first min(total, cap) records, the total
+ *   is returned (or a b2hip_status): when it exceeds cap, call again with cap = the total - exactly as b2hip_query_aabbs.
+ * b2hip_body_contact_totals: one record per body over its TOUCHING records: contacts counts every entry of
+ *   b2hip_get_contacts that names the body, touching those of them that touch; impulse is the sum of the touching records'
+ *   impulse vectors (above), normal_impulse the sum and max_normal_impulse the largest of their normal_impulse (0 without a
+ *   touching contact), points the sum of their point_count, pad 0. The sums are fp32, formed in an order that depends only on
+ *   the body's list (no float atomics anywhere); the order is otherwise not part of the contract. Returns B2HIP_OK or a
+ *   b2hip_status. A destroyed body, or one without contacts, has an all-zero total.
+ * Argument errors, refused with B2HIP_ERR_INVALID before any device work and before the world is looked at, in this order:
+ *   n outside [0, 2^24]; a negative cap; a NULL offsets / out, NULL bodies with n > 0, NULL records with cap > 0. Then the
+ *   world: a NULL world, or a call inside an open step, B2HIP_ERR_INVALID; a sharded world (b2hip_set_shard with more than one
+ *   rank, b2hip_shard_spatial) B2HIP_ERR_UNSUPPORTED. Then the ids, on the host, before any device work: an id outside
+ *   [0, b2hip_body_count) or one that occurs twice is B2HIP_ERR_INVALID, and b2hip_last_error names the first offender.
+ *   n == 0 writes offsets[0] = 0 and returns 0.
+ * Cost: two passes over the world's contact array (20 bytes a contact each: ids and flags), a scan over the batch, a sort of
+ *   each body's list in LDS, then one thread per record (lists) or one wave per body (totals). A body with more than 4096
+ *   listed contacts (a container, a ground under a crowd) is ordered by marking its contacts in a flag per contact of the
+ *   world and compacting the flags from ONE workgroup, one such body after the other from the host: correct, and slow. */
+typedef struct b2hip_body_contact       /* 32 bytes */
+{
+	int32_t contact_index;          /* index into b2hip_get_contacts called at the same point */
+	int32_t other_body;
+	int32_t fixture, other_fixture; /* this body's fixture id, the other body's (a chain child is its own id) */
+	float normal[2];                /* world manifold normal, pointing from the other body towards this one */
+	float normal_impulse;           /* sum over the manifold points j < point_count */
+	float tangent_impulse;          /* likewise */
+} b2hip_body_contact;
+
+typedef struct b2hip_body_contact_total /* 32 bytes */
+{
+	int32_t contacts;               /* entries of b2hip_get_contacts that name the body */
+	int32_t touching;               /* of those, touching (flags bit0) */
+	float impulse[2];               /* net impulse the touching contacts put on this body in the last step, world frame */
+	float normal_impulse;           /* sum of the touching records' normal_impulse */
+	float max_normal_impulse;       /* largest of them; 0 with no touching contact */
+	int32_t points;                 /* manifold points of the touching contacts */
+	int32_t pad;                    /* 0 */
+} b2hip_body_contact_total;
+
+int b2hip_body_contacts(b2hip_world* w, int n, const int32_t* bodies, int touching_only, int cap, int32_t* offsets /* n + 1 */,
+                        b2hip_body_contact* records /* cap */);
+int b2hip_body_contact_totals(b2hip_world* w, int n, const int32_t* bodies, b2hip_body_contact_total* out /* n */);
+
 #ifdef __cplusplus
 }
 #endif
