@@ -34,6 +34,7 @@
 #include "b2d_kernels_spatial.h"
 #include "b2d_kernels_query.h"
 #include "b2d_kernels_body_contacts.h"
+#include "b2d_kernels_body_writes.h"
 #include "b2d_scan.h"
 #include "b2d_shape_geom.h"
 
@@ -53,4 +54,5 @@ extern "C"
 #include "b2hip_api_callbacks.h"
 #include "b2hip_api_query.h"
 #include "b2hip_api_body_contacts.h"
+#include "b2hip_api_body_writes.h"
 } // extern "C"

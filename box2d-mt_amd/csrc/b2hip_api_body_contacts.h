@@ -31,8 +31,10 @@ static int bodyContactsArgs(const char* what, int n, const int32_t* bodies, int 
 	return 0;
 }
 
-// the ids, on the host: each in [0, body count), each once; the first offender is named
-static int bodyContactsIds(b2hip_world* w, const char* what, int n, const int32_t* bodies)
+// the ids, on the host: each in [0, body count), each once; the first offender is named. The batched body writes and the
+// state gather (b2hip_api_body_writes.h) check theirs here too: `alive` refuses a destroyed body as well, `unique` false
+// lets an id occur again (a read).
+static int bodyContactsIds(b2hip_world* w, const char* what, int n, const int32_t* bodies, bool alive = false, bool unique = true)
 {
 	const size_t nb = w->bodies.size();
 	if (w->bcSeen.size() < nb) w->bcSeen.resize(nb, 0u);
@@ -47,6 +49,9 @@ static int bodyContactsIds(b2hip_world* w, const char* what, int n, const int32_
 		if (b < 0 || (size_t)b >= nb)
 			return setError(B2HIP_ERR_INVALID, std::string(what) + ": entry " + std::to_string(i) + " names body " + std::to_string(b) +
 			                ", outside [0, b2hip_body_count)");
+		if (alive && w->bodies[(size_t)b].dead)
+			return setError(B2HIP_ERR_INVALID, std::string(what) + ": entry " + std::to_string(i) + " names body " + std::to_string(b) + ", which is destroyed");
+		if (!unique) continue;
 		if (w->bcSeen[(size_t)b] == w->bcEpoch)
 			return setError(B2HIP_ERR_INVALID, std::string(what) + ": entry " + std::to_string(i) + " names body " + std::to_string(b) + " a second time");
 		w->bcSeen[(size_t)b] = w->bcEpoch;

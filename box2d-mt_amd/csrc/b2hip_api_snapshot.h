@@ -62,6 +62,7 @@ int b2hip_save_snapshot(b2hip_world* w, void* buffer, size_t cap, size_t* needed
 	if (int rcu = checkUsable(w, "b2hip_save_snapshot", true)) return rcu;
 	DEVICE_GUARD(w);
 	ensureRows(w); // (the snapshot carries the host's mirror)
+	pullDeviceForces(w); // (... and forces a batched write left on the device belong to it)
 	int rc = flushEdits(w); // everything the host has created or edited is on the device now
 	if (rc) return rc;
 	rc = applyPendingFilters(w); // ... including the re-filter flags of joints created / destroyed since the last step

@@ -76,6 +76,8 @@ struct HostBody
 	bool dirty;
 	uint32_t pullEpoch;  // == b2hip_world::mirrorEpoch: this row has been refreshed from (or is newer than) h_state
 	uint32_t forceEpoch; // == b2hip_world::stepEpoch: fx, fy, torque were applied since the last step (auto-clear worlds)
+	uint32_t forceDev;   // != 0: a batched write named the body at this stepEpoch, and its b_force row on the device is the newer
+	                     // copy of fx, fy, torque (the read-back row does not carry them): fetched by the next pullBody
 };
 
 struct HostFixture
@@ -258,6 +260,11 @@ struct b2hip_world
 	DevArray<b2hip_body_contact_total> bcTotals;
 	std::vector<uint32_t> bcSeen;
 	uint32_t bcEpoch = 0;
+	// batched body writes and the state gather (b2hip_api_body_writes.h): the batch's records / the gathered rows on the device
+	// (the ids share bcIds); forceDevCount: bodies whose force row on the device is newer than the host's (HostBody::forceDev)
+	DevArray<float4> bwIn;
+	DevArray<float2> bwRows;
+	size_t forceDevCount = 0;
 	ScanFlags qScan;
 	void* qPinned = nullptr;
 	size_t qPinnedBytes = 0;
@@ -531,6 +538,35 @@ static int nextPow2(size_t n)
 // The read-back buffer h_state IS the host mirror of the dynamic state; a HostBody is refreshed from it only
 // when the host is about to edit that body (no O(bodies) host loop per step).
 static void ensureRows(b2hip_world* w);
+
+// The read-back row carries no forces: HostBody::fx, fy, torque are their only host copy, and the next upload of the body
+// overwrites b_force from them. Behind a batched write (b2hip_api_body_writes.h) the device's row is the newer one - whatever
+// it holds by now - and this brings it home, 16 bytes, when the host is about to edit the body. In an auto-clear world a step
+// since the batch has cleared the row: the mark is dropped, and the zeros pullBody has just written are the truth.
+static void pullForce(b2hip_world* w, int i)
+{
+	HostBody& b = w->bodies[i];
+	const bool live = !w->def.auto_clear_forces || b.forceDev == w->stepEpoch;
+	b.forceDev = 0u;
+	{
+		std::lock_guard<std::mutex> lock(w->dirtyMutex);
+		w->forceDevCount -= 1;
+	}
+	if (!live) return;
+	float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+	DeviceGuard guard(w->device);
+	hipError_t e = hipMemcpyAsync(&f, w->b_force.p + i, sizeof(float4), hipMemcpyDeviceToHost, w->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
+	if (e != hipSuccess)
+	{
+		// (the force cannot be had: the world is as good as lost - every later call says why, as with ensureRows)
+		w->failed = true;
+		w->failedWhy = std::string("reading a body's force row: ") + hipGetErrorString(e);
+		return;
+	}
+	b.fx = f.x; b.fy = f.y; b.torque = f.z;
+}
+
 static void pullBody(b2hip_world* w, int i)
 {
 	if ((size_t)i >= w->stateCount || w->h_state == nullptr) return;
@@ -553,6 +589,14 @@ static void pullBody(b2hip_world* w, int i)
 	b.qc = cosf(b.a);
 	if (w->def.auto_clear_forces && b.forceEpoch != w->stepEpoch) { b.fx = b.fy = b.torque = 0.0f; }
 	b.forceEpoch = w->stepEpoch;
+	if (b.forceDev != 0u) pullForce(w, i);
+}
+
+// Whoever copies the HostBody rows out as they are (the snapshot) pulls the bodies whose forces live on the device first.
+static void pullDeviceForces(b2hip_world* w)
+{
+	for (size_t i = 0; i < w->bodies.size() && w->forceDevCount > 0; ++i)
+		if (w->bodies[i].forceDev != 0u && !w->bodies[i].dirty) pullBody(w, (int)i);
 }
 
 static void markDirty(b2hip_world* w, int i)

@@ -143,6 +143,8 @@ BODY_CONTACT_DTYPE = np.dtype([("contact_index", "i4"), ("other_body", "i4"), ("
                                ("normal", "f4", 2), ("normal_impulse", "f4"), ("tangent_impulse", "f4")])
 BODY_CONTACT_TOTAL_DTYPE = np.dtype([("contacts", "i4"), ("touching", "i4"), ("impulse", "f4", 2), ("normal_impulse", "f4"),
                                      ("max_normal_impulse", "f4"), ("points", "i4"), ("pad", "i4")])
+BODY_PUSH_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("angular", "f4"), ("at_point", "i4"), ("px", "f4"), ("py", "f4"),
+                            ("pad", "i4", 2)])
 
 _lib = None
 
@@ -221,6 +223,13 @@ def _configure(L, optional_ok=False):
                                       C.c_void_p, C.c_void_p],
         "b2hip_body_contacts": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_body_contact_totals": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_apply_linear_impulse": [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int],
+        "b2hip_apply_linear_impulse_to_center": [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int],
+        "b2hip_apply_angular_impulse": [C.c_void_p, C.c_int, C.c_float, C.c_int],
+        "b2hip_apply_forces": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
+        "b2hip_apply_impulses": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
+        "b2hip_set_velocities": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
+        "b2hip_get_body_states_of": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     }
     for name, argtypes in sigs.items():
         try:
@@ -498,6 +507,15 @@ class World:
     def apply_force(self, body, force=(0.0, 0.0), torque=0.0, wake=True):
         _check(self.L.b2hip_apply_force(self.p, body, force[0], force[1], torque, int(wake)))
 
+    def apply_linear_impulse(self, body, impulse, point, wake=True):
+        _check(self.L.b2hip_apply_linear_impulse(self.p, body, impulse[0], impulse[1], point[0], point[1], int(wake)))
+
+    def apply_linear_impulse_to_center(self, body, impulse, wake=True):
+        _check(self.L.b2hip_apply_linear_impulse_to_center(self.p, body, impulse[0], impulse[1], int(wake)))
+
+    def apply_angular_impulse(self, body, impulse, wake=True):
+        _check(self.L.b2hip_apply_angular_impulse(self.p, body, impulse, int(wake)))
+
     def set_flags(self, allow_sleep=True, warm_starting=True, continuous=False, sub_stepping=False):
         _check(self.L.b2hip_set_flags(self.p, int(allow_sleep), int(warm_starting), int(continuous), int(sub_stepping)))
 
@@ -744,6 +762,81 @@ class World:
         b = self._body_ids(bodies)
         out = np.zeros(len(b), BODY_CONTACT_TOTAL_DTYPE)
         _check(self.L.b2hip_body_contact_totals(self.p, len(b), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    # ---- batched body writes on the device (include/b2hip.h, block F: b2hip_apply_forces, b2hip_apply_impulses,
+    # b2hip_set_velocities, b2hip_get_body_states_of)
+    @classmethod
+    def _pushes(cls, n, linear, angular, point, name):
+        """n BODY_PUSH_DTYPE records: `linear` (n, 2) or one pair, `angular` (n,) or one number, `point` None (at the centre
+        of mass), (n, 2) or one pair."""
+        push = np.zeros(n, BODY_PUSH_DTYPE)
+        lin = np.asarray(linear, np.float32)
+        lin = cls._pairs(np.broadcast_to(lin, (n, 2)) if lin.ndim == 1 and lin.shape == (2,) else lin, name)
+        ang = np.asarray(angular, np.float32)
+        if ang.ndim > 1 or (ang.ndim == 1 and len(ang) != n) or len(lin) != n:
+            raise ValueError("%s: %d bodies, %d vectors, angular of shape %s" % (name, n, len(lin), ang.shape))
+        push["x"], push["y"], push["angular"] = lin[:, 0], lin[:, 1], ang
+        if point is not None:
+            pt = np.asarray(point, np.float32)
+            pt = cls._pairs(np.broadcast_to(pt, (n, 2)) if pt.ndim == 1 and pt.shape == (2,) else pt, "point")
+            if len(pt) != n:
+                raise ValueError("point: %d bodies, %d points" % (n, len(pt)))
+            push["at_point"], push["px"], push["py"] = 1, pt[:, 0], pt[:, 1]
+        return push
+
+    def _push(self, fn, bodies, push, wake):
+        b = self._body_ids(bodies)
+        push = np.ascontiguousarray(push, BODY_PUSH_DTYPE)
+        if push.shape != b.shape:
+            raise ValueError("%d bodies, push records of shape %s" % (len(b), push.shape))
+        _check(fn(self.p, len(b), b.ctypes.data_as(C.c_void_p), push.ctypes.data_as(C.c_void_p), int(bool(wake))))
+
+    def apply_forces(self, bodies, force, torque=0.0, point=None, wake=True):
+        """b2hip_apply_force for each body of `bodies` (ids, each once) in one call on the device: `force` (n, 2) or one pair
+        for all, `torque` (n,) or one number, `point` (n, 2) or one pair: the world points the forces act at (None: the
+        centres of mass). `force` may also be a BODY_PUSH_DTYPE array (then torque and point are not looked at)."""
+        b = self._body_ids(bodies)
+        if not (isinstance(force, np.ndarray) and force.dtype == BODY_PUSH_DTYPE):
+            force = self._pushes(len(b), force, torque, point, "force")
+        self._push(self.L.b2hip_apply_forces, b, force, wake)
+
+    def apply_impulses(self, bodies, impulse, angular=0.0, point=None, wake=True):
+        """The linear impulse call (at `point`, or at the centre of mass) and then b2hip_apply_angular_impulse for each body of
+        `bodies` (ids, each once) in one call on the device; arguments as apply_forces."""
+        b = self._body_ids(bodies)
+        if not (isinstance(impulse, np.ndarray) and impulse.dtype == BODY_PUSH_DTYPE):
+            impulse = self._pushes(len(b), impulse, angular, point, "impulse")
+        self._push(self.L.b2hip_apply_impulses, b, impulse, wake)
+
+    def set_velocities(self, bodies, velocity=None, omega=None):
+        """b2hip_set_velocity for each body of `bodies` (ids, each once) in one call on the device: `velocity` (n, 2) or one
+        pair, `omega` (n,) or one number; what is None keeps its value."""
+        if velocity is None and omega is None:
+            raise ValueError("set_velocities: neither a velocity nor an omega")
+        b = self._body_ids(bodies)
+        n = len(b)
+        v3 = np.zeros((n, 3), np.float32)
+        if velocity is not None:
+            v = np.asarray(velocity, np.float32)
+            v = self._pairs(np.broadcast_to(v, (n, 2)) if v.ndim == 1 and v.shape == (2,) else v, "velocity")
+            if len(v) != n:
+                raise ValueError("velocity: %d bodies, %d vectors" % (n, len(v)))
+            v3[:, :2] = v
+        if omega is not None:
+            o = np.asarray(omega, np.float32)
+            if o.ndim > 1 or (o.ndim == 1 and len(o) != n):
+                raise ValueError("omega: %d bodies, shape %s" % (n, o.shape))
+            v3[:, 2] = o
+        mask = (1 if velocity is not None else 0) | (2 if omega is not None else 0)
+        _check(self.L.b2hip_set_velocities(self.p, n, b.ctypes.data_as(C.c_void_p), v3.ctypes.data_as(C.c_void_p), mask))
+
+    def body_states_of(self, bodies):
+        """The BODY_STATE_DTYPE rows of `bodies` (ids; one may occur again), gathered on the device: body_states()[bodies]
+        without the table crossing."""
+        b = self._body_ids(bodies)
+        out = np.zeros(len(b), BODY_STATE_DTYPE)
+        _check(self.L.b2hip_get_body_states_of(self.p, len(b), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def solver_timing(self):

@@ -993,6 +993,58 @@ int b2hip_body_contacts(b2hip_world* w, int n, const int32_t* bodies, int touchi
                         b2hip_body_contact* records /* cap */);
 int b2hip_body_contact_totals(b2hip_world* w, int n, const int32_t* bodies, b2hip_body_contact_total* out /* n */);
 
+/* ---- F. Batched body writes on the device (csrc/b2hip_api_body_writes.h, csrc/b2d_kernels_body_writes.h) ---------------------
+ * Push many bodies between two steps in one call: the control loop of many agents, a crowd, wind, an explosion. The
+ * single-body calls (b2hip_apply_force, b2hip_set_velocity, b2hip_apply_*_impulse) edit the host's mirror, and the next step
+ * uploads eight rows per edited body; these calls edit the device's rows in one launch and the host's mirror follows.
+ *
+ * Definition by equivalence. Each write call has the effect of the existing single-body calls made for i = 0 .. n-1 in
+ * order, to the bit, for everything a caller can observe afterwards: b2hip_get_body_states, later single-body edits,
+ * snapshots, every later step. With s the state b2hip_get_body_states reports for bodies[i] at the call:
+ *   b2hip_apply_forces:   b2hip_apply_force(w, b, x, y, T, wake) with T = angular when at_point == 0, else
+ *                         T = angular + ((px - s.cx) * y - (py - s.cy) * x) in float32, in that operation order.
+ *   b2hip_apply_impulses: first the linear call - b2hip_apply_linear_impulse_to_center(w, b, x, y, wake) when at_point == 0,
+ *                         b2hip_apply_linear_impulse(w, b, x, y, px, py, wake) otherwise - then
+ *                         b2hip_apply_angular_impulse(w, b, angular, wake). Both are always made: a zero still does its +=.
+ *   b2hip_set_velocities: b2hip_set_velocity(w, b, vx', vy', w') with the primed values from v3 where the mask bit is set
+ *                         (bit 0: the linear velocity, bit 1: the angular velocity) and from s where it is not; the wake rule
+ *                         of b2hip_set_velocity (a non-zero velocity wakes the body and restarts its sleep timer) is applied
+ *                         to the primed values.
+ *   So: forces and impulses skip bodies that are not dynamic, velocities skip static bodies; a sleeping body with wake == 0 is
+ *   left alone; waking sets the awake flag and zeroes the sleep time.
+ * Order: edits made before the call lie underneath it and edits made after it on top of it, as in the loop: a single
+ *   b2hip_apply_force after b2hip_apply_forces adds to the batch's sum, a b2hip_set_velocity replaces the batch's velocity.
+ *   Two write calls before one step act one after the other.
+ * bodies: n body ids, each in [0, b2hip_body_count), not destroyed, and each AT MOST ONCE per write call - that is what makes
+ *   a call deterministic without atomics. (To push a body twice, make two calls.)
+ * b2hip_get_body_states_of: the b2hip_body_state rows of n bodies - out[i] is what b2hip_get_body_states reports for
+ *   bodies[i] at the same moment - gathered on the device: n x 40 bytes cross, not the table, whatever
+ *   b2hip_set_lazy_readback says and without fetching the table. A read: an id may occur more than once.
+ * Argument errors, refused with B2HIP_ERR_INVALID before the world is looked at, in this order: n outside [0, 2^24]; a NULL
+ *   bodies / push / v3 with n > 0, a NULL out; a mask other than 1, 2 or 3. Then the world: a NULL world, or a call inside an
+ *   open step (a listener's callback window included), B2HIP_ERR_INVALID; a sharded world (b2hip_set_shard with more than one
+ *   rank, b2hip_shard_spatial) B2HIP_ERR_UNSUPPORTED. Then the ids, on the host, before any device work: an id out of range, a
+ *   destroyed body or (write calls) an id that occurs twice is B2HIP_ERR_INVALID, and b2hip_last_error names the first
+ *   offender by entry and id. A refused call applies nothing. n == 0 is a successful no-op. All four return B2HIP_OK or a
+ *   b2hip_status.
+ * Cost: the ids and records cross in one copy, one launch edits one body per lane, and the call returns when the device is
+ *   done; nothing comes back. The body-state table is not fetched: the rows are marked as newer on the device, and the next
+ *   b2hip_get_body_states (or single-body edit) fetches the rows that changed. */
+typedef struct b2hip_body_push {        /* 32 bytes */
+	float   x, y;        /* force [N] or linear impulse [N s], world frame */
+	float   angular;     /* torque [N m] or angular impulse */
+	int32_t at_point;    /* 0: at the centre of mass; 1: at the world point (px, py) */
+	float   px, py;
+	int32_t pad[2];
+} b2hip_body_push;
+
+int b2hip_apply_forces  (b2hip_world* w, int n, const int32_t* bodies, const b2hip_body_push* push, int wake);
+int b2hip_apply_impulses(b2hip_world* w, int n, const int32_t* bodies, const b2hip_body_push* push, int wake);
+/* v3: n x (vx, vy, omega); mask bit 0: set the linear velocity, bit 1: set the angular velocity (1, 2 or 3) */
+int b2hip_set_velocities(b2hip_world* w, int n, const int32_t* bodies, const float* v3, int mask);
+/* the b2hip_body_state rows of n bodies, gathered on the device: n x 40 bytes cross, not the table */
+int b2hip_get_body_states_of(b2hip_world* w, int n, const int32_t* bodies, b2hip_body_state* out);
+
 #ifdef __cplusplus
 }
 #endif
