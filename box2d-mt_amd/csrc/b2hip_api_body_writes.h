@@ -41,12 +41,15 @@ static int bodyWritesBegin(b2hip_world* w, int n, const int32_t* bodies, const v
 	if (rc) return rc;
 	hipStream_t s = w->stream;
 	const size_t idBytes = (((size_t)n * sizeof(int32_t)) + 15) & ~(size_t)15; // (the records start 16-byte aligned)
-	rc = w->bcIds.ensure((size_t)n, s, false, false);
+	rc = n ? w->bcIds.ensure((size_t)n, s, false, false) : 0;
 	if (!rc && bytes) rc = w->bwIn.ensure((bytes + sizeof(float4) - 1) / sizeof(float4), s, false, false);
 	if (!rc) rc = queryPinned(w, std::max(idBytes + bytes, atLeast));
 	if (rc) return rc;
-	memcpy(w->qPinned, bodies, (size_t)n * sizeof(int32_t));
-	HIP_TRY(hipMemcpyAsync(w->bcIds.p, w->qPinned, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	if (n) // (none: the records name their targets themselves - the motor edits of b2hip_api_joint_batch.h)
+	{
+		memcpy(w->qPinned, bodies, (size_t)n * sizeof(int32_t));
+		HIP_TRY(hipMemcpyAsync(w->bcIds.p, w->qPinned, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	}
 	if (bytes)
 	{
 		memcpy((char*)w->qPinned + idBytes, records, bytes);

@@ -265,6 +265,11 @@ struct b2hip_world
 	DevArray<float4> bwIn;
 	DevArray<float2> bwRows;
 	size_t forceDevCount = 0;
+	// batched joints (b2hip_api_joint_batch.h): the gathered joint states on the device (the ids share bcIds, the motor edits
+	// bwIn); jbSeen / jbEpoch: the host's duplicate check of a write call's joint ids
+	DevArray<float4> jbOut;
+	std::vector<uint32_t> jbSeen;
+	uint32_t jbEpoch = 0;
 	ScanFlags qScan;
 	void* qPinned = nullptr;
 	size_t qPinnedBytes = 0;

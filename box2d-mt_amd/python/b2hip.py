@@ -145,6 +145,10 @@ BODY_CONTACT_TOTAL_DTYPE = np.dtype([("contacts", "i4"), ("touching", "i4"), ("i
                                      ("max_normal_impulse", "f4"), ("points", "i4"), ("pad", "i4")])
 BODY_PUSH_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("angular", "f4"), ("at_point", "i4"), ("px", "f4"), ("py", "f4"),
                             ("pad", "i4", 2)])
+JOINT_MOTOR_DTYPE = np.dtype([("enable_motor", "i4"), ("motor_speed", "f4"), ("max_motor", "f4"), ("pad", "i4")])
+JOINT_STATE_DTYPE = np.dtype([("type", "i4"), ("limit_state", "i4"), ("coordinate", "f4"), ("speed", "f4"), ("coordinate2", "f4"),
+                              ("speed2", "f4"), ("force", "f4", 2), ("torque", "f4"), ("motor", "f4"), ("pad", "f4", 2)])
+JOINT_MOTOR_ENABLE, JOINT_MOTOR_SPEED, JOINT_MOTOR_MAX = 1, 2, 4  # the mask bits of b2hip_joint_set_motors
 
 _lib = None
 
@@ -230,6 +234,12 @@ def _configure(L, optional_ok=False):
         "b2hip_apply_impulses": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
         "b2hip_set_velocities": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
         "b2hip_get_body_states_of": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_get_joint_reaction": [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)],
+        "b2hip_get_joint_limit_state": [C.c_void_p, C.c_int],
+        "b2hip_joint_count": [C.c_void_p],
+        "b2hip_joint_is_destroyed": [C.c_void_p, C.c_int],
+        "b2hip_joint_set_motors": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
+        "b2hip_get_joint_states": [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p],
     }
     for name, argtypes in sigs.items():
         try:
@@ -837,6 +847,77 @@ class World:
         b = self._body_ids(bodies)
         out = np.zeros(len(b), BODY_STATE_DTYPE)
         _check(self.L.b2hip_get_body_states_of(self.p, len(b), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    # ---- batched joints on the device (include/b2hip.h, block G: b2hip_joint_set_motors, b2hip_get_joint_states) and the
+    # single-joint reads they are defined by
+    @property
+    def joint_count(self):
+        return self.L.b2hip_joint_count(self.p)
+
+    def joint_is_destroyed(self, joint):
+        return bool(self.L.b2hip_joint_is_destroyed(self.p, joint))
+
+    def joint_reaction(self, joint, inv_dt=60.0):
+        """b2hip_get_joint_reaction: (force x, force y, torque, motor torque / force) of the last step as 4 float32."""
+        out = np.zeros(4, np.float32)
+        _check(self.L.b2hip_get_joint_reaction(self.p, joint, inv_dt, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def joint_limit_state(self, joint):
+        """b2hip_get_joint_limit_state: 0 inactive, 1 at lower, 2 at upper, 3 equal limits."""
+        return _check(self.L.b2hip_get_joint_limit_state(self.p, joint))
+
+    @staticmethod
+    def _joint_ids(joints):
+        j = np.ascontiguousarray(joints, np.int32)
+        if j.ndim != 1:
+            raise ValueError("joints: an (n,) array of joint ids is expected, got shape %s" % (j.shape,))
+        return j
+
+    @staticmethod
+    def _joint_motors(n, speed, max_motor, enable):
+        """(n JOINT_MOTOR_DTYPE records, mask) of what is given: each of `speed`, `max_motor`, `enable` None (the joint keeps its
+        value), one number for all, or (n,)."""
+        motors = np.zeros(n, JOINT_MOTOR_DTYPE)
+        mask = 0
+        for value, field, bit, kind in ((enable, "enable_motor", JOINT_MOTOR_ENABLE, bool), (speed, "motor_speed", JOINT_MOTOR_SPEED, np.float32),
+                                        (max_motor, "max_motor", JOINT_MOTOR_MAX, np.float32)):
+            if value is None:
+                continue
+            v = np.asarray(value, kind)
+            if v.ndim > 1 or (v.ndim == 1 and len(v) != n):
+                raise ValueError("%s: %d joints, shape %s" % (field, n, v.shape))
+            motors[field] = v
+            mask |= bit
+        if mask == 0:
+            raise ValueError("joint_set_motors: none of speed, max_motor and enable is given")
+        return motors, mask
+
+    def joint_set_motors(self, joints, speed=None, max_motor=None, enable=None, mask=None):
+        """b2hip_joint_set_motor for each joint of `joints` (revolute, prismatic or wheel; ids, each once) in one call on the
+        device: `speed`, `max_motor` and `enable` are one value for all or (n,); what is None keeps its value. `speed` may also
+        be a JOINT_MOTOR_DTYPE array, taken as it is with an explicit mask= (1: enable_motor, 2: motor_speed, 4: max_motor)."""
+        j = self._joint_ids(joints)
+        if isinstance(speed, np.ndarray) and speed.dtype == JOINT_MOTOR_DTYPE:
+            if mask is None or max_motor is not None or enable is not None:
+                raise ValueError("joint_set_motors: a JOINT_MOTOR_DTYPE array goes with mask= and nothing else")
+            motors = np.ascontiguousarray(speed)
+            if motors.shape != j.shape:
+                raise ValueError("%d joints, motor records of shape %s" % (len(j), motors.shape))
+        else:
+            if mask is not None:
+                raise ValueError("joint_set_motors: mask= goes with a JOINT_MOTOR_DTYPE array only")
+            motors, mask = self._joint_motors(len(j), speed, max_motor, enable)
+        _check(self.L.b2hip_joint_set_motors(self.p, len(j), j.ctypes.data_as(C.c_void_p), motors.ctypes.data_as(C.c_void_p), int(mask)))
+
+    def joint_states(self, joints, inv_dt=60.0):
+        """One JOINT_STATE_DTYPE record per joint of `joints` (ids; one may occur again), computed on the device: type (-1:
+        destroyed), limit state, the joint's coordinate(s) and speed(s), and the reaction force, torque and motor share of the
+        last step scaled by inv_dt."""
+        j = self._joint_ids(joints)
+        out = np.zeros(len(j), JOINT_STATE_DTYPE)
+        _check(self.L.b2hip_get_joint_states(self.p, len(j), j.ctypes.data_as(C.c_void_p), inv_dt, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def solver_timing(self):

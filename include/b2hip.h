@@ -1045,6 +1045,74 @@ int b2hip_set_velocities(b2hip_world* w, int n, const int32_t* bodies, const flo
 /* the b2hip_body_state rows of n bodies, gathered on the device: n x 40 bytes cross, not the table */
 int b2hip_get_body_states_of(b2hip_world* w, int n, const int32_t* bodies, b2hip_body_state* out);
 
+/* ---- G. Batched joints on the device (csrc/b2hip_api_joint_batch.h, csrc/b2d_kernels_joint_batch.h) -------------------------
+ * Drive and read many joints between two steps in one call each: the motor targets of arms, cars, ragdolls and walkers, and
+ * what their joints did. b2hip_joint_set_motor queues one upload per joint and puts both bodies through the host's mirror
+ * (eight rows uploaded per body); b2hip_get_joint_reaction and b2hip_get_joint_limit_state copy and wait once per joint. These
+ * calls do either in one launch.
+ *
+ * b2hip_joint_set_motors. mask bit 1: enable_motor, bit 2: motor_speed, bit 4: max_motor (max_motor is the maximum motor
+ *   torque of a revolute or wheel joint, the maximum motor force of a prismatic joint).
+ *   Definition by equivalence: the call has the effect of b2hip_joint_set_motor(w, joints[i], e', s', m') made for
+ *   i = 0 .. n-1 in order, with a primed value from motors[i] where its mask bit is set and otherwise the value the joint
+ *   currently has (what a preceding b2hip_joint_set_motor or batch left) - to the bit, for everything a caller can observe
+ *   afterwards: b2hip_get_body_states, b2hip_get_joint_states, later single edits, snapshots, every later step.
+ *   So: an entry whose primed triple equals the current one does nothing and wakes nobody. An entry that changes its joint
+ *   does b2Body::SetAwake(true) on both of its bodies: the awake flag is set and the sleep time zeroed whether or not the
+ *   body slept; a static body that is awake already is left untouched. Joints of one batch may share bodies (a chain, a
+ *   chassis with two wheels): every writer stores the same values, so the result does not depend on the order of the lanes.
+ *   joints: n joint ids, each in [0, b2hip_joint_count), not destroyed, revolute, prismatic or wheel, and each AT MOST ONCE per
+ *   call. (To set a joint twice, make two calls.)
+ *   Order: edits made before the call lie underneath it and edits made after it on top of it, as in the loop: a
+ *   b2hip_joint_set_motor before a batch whose mask omits the speed keeps its speed, a b2hip_joint_set_limits after a batch
+ *   keeps the batch's motor. Two calls before one step act one after the other.
+ * b2hip_get_joint_states. A read: an id may occur more than once and the world is not changed. Per entry:
+ *   type         the joint's type (0 revolute, 1 distance, 2 prismatic, 3 weld, 4 wheel, 5 rope, 6 friction, 7 motor,
+ *                8 pulley, 9 mouse, 10 gear). A destroyed joint gives -1 and zeros in every other member.
+ *   limit_state  what b2hip_get_joint_limit_state returns at that moment.
+ *   force, torque, motor   what b2hip_get_joint_reaction(w, joint, inv_dt, ..) returns, to the bit. inv_dt is taken as given.
+ *   coordinate, speed, coordinate2, speed2   the getters of the joint classes, in float32, from the bodies' current states:
+ *                revolute   GetJointAngle (aB - aA - reference angle), GetJointSpeed (wB - wA), 0, 0
+ *                prismatic  GetJointTranslation, GetJointSpeed, 0, 0
+ *                wheel      GetJointTranslation, GetJointLinearSpeed, GetJointAngle (aB - aA), GetJointAngularSpeed
+ *                pulley     GetCurrentLengthA, 0, GetCurrentLengthB, 0
+ *                every other type: zeros
+ *   Body edits made since the step (b2hip_set_transform, a batched velocity set) are seen: the pending edits are uploaded
+ *   before the launch. A joint created since the last step reports a zero reaction and its coordinates from the bodies.
+ * Argument errors, refused with B2HIP_ERR_INVALID before the world is looked at, in this order: n outside [0, 2^24]; a NULL
+ *   joints / motors with n > 0, a NULL out; a mask outside 1..7. Then the world: a NULL world, or a call inside an open step (a
+ *   listener's callback window included), B2HIP_ERR_INVALID; a sharded world (b2hip_set_shard with more than one rank,
+ *   b2hip_shard_spatial) B2HIP_ERR_UNSUPPORTED. Then the ids, on the host, before any device work: an id outside
+ *   [0, b2hip_joint_count), and for b2hip_joint_set_motors a destroyed joint, a joint whose type has no motor or an id that
+ *   occurs twice, is B2HIP_ERR_INVALID, and b2hip_last_error names the first offender by entry and id. A refused call
+ *   applies nothing. n == 0 is a successful no-op. Both return B2HIP_OK or a b2hip_status.
+ * Cost: b2hip_joint_set_motors sends the entries that change (16 bytes each) in one copy, one launch edits one joint per lane,
+ *   and the call returns when the device is done; nothing comes back, and the body-state table is not fetched (the woken
+ *   bodies' rows are marked as newer on the device). b2hip_get_joint_states sends 4 bytes and fetches 48 bytes per entry.
+ * b2hip_joint_count: joints ever created (ids are never reused); b2hip_joint_is_destroyed: 1 for a destroyed joint, else 0. */
+typedef struct b2hip_joint_motor {      /* 16 bytes */
+	int32_t enable_motor;
+	float   motor_speed;
+	float   max_motor;   /* maximum motor torque (revolute, wheel) or force (prismatic) */
+	int32_t pad;
+} b2hip_joint_motor;
+
+typedef struct b2hip_joint_state {      /* 48 bytes */
+	int32_t type;        /* -1: destroyed */
+	int32_t limit_state; /* b2hip_get_joint_limit_state */
+	float   coordinate, speed;
+	float   coordinate2, speed2;
+	float   force[2];    /* b2hip_get_joint_reaction: on bodyB at the anchor */
+	float   torque;
+	float   motor;
+	float   pad[2];      /* 0 */
+} b2hip_joint_state;
+
+int b2hip_joint_count(const b2hip_world* w);
+int b2hip_joint_is_destroyed(const b2hip_world* w, int joint);
+int b2hip_joint_set_motors(b2hip_world* w, int n, const int32_t* joints, const b2hip_joint_motor* motors, int mask);
+int b2hip_get_joint_states(b2hip_world* w, int n, const int32_t* joints, float inv_dt, b2hip_joint_state* out);
+
 #ifdef __cplusplus
 }
 #endif
