@@ -96,7 +96,7 @@ int b2hip_joint_set_motors(b2hip_world* w, int n, const int32_t* joints, const b
 		memcpy(&j.motorSpeed, &edits[(size_t)k].z, sizeof(float));
 		memcpy(&j.maxMotorTorque, &edits[(size_t)k].w, sizeof(float));
 	}
-	return bodyWritesMirror(w, (int)woken.size(), woken.data(), false);
+	return bodyWritesMirror(w, (int)woken.size(), woken.data(), BODY_FORCES_NONE);
 }
 
 int b2hip_get_joint_states(b2hip_world* w, int n, const int32_t* joints, float inv_dt, b2hip_joint_state* out)

@@ -234,6 +234,9 @@ def _configure(L, optional_ok=False):
         "b2hip_apply_impulses": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
         "b2hip_set_velocities": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
         "b2hip_get_body_states_of": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_set_transform": [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float],
+        "b2hip_set_transforms": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
+        "b2hip_set_awakes": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_get_joint_reaction": [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)],
         "b2hip_get_joint_limit_state": [C.c_void_p, C.c_int],
         "b2hip_joint_count": [C.c_void_p],
@@ -495,6 +498,10 @@ class World:
 
     def set_awake(self, body, flag=True):
         _check(self.L.b2hip_set_awake(self.p, body, int(flag)))
+
+    def set_transform(self, body, position, angle):
+        """b2Body::SetTransform: the body's origin and angle; it keeps its velocity and does not wake."""
+        _check(self.L.b2hip_set_transform(self.p, body, position[0], position[1], angle))
 
     def fixture_set_sensor(self, fixture, flag=True):
         _check(self.L.b2hip_fixture_set_sensor(self.p, fixture, int(flag)))
@@ -848,6 +855,41 @@ class World:
         out = np.zeros(len(b), BODY_STATE_DTYPE)
         _check(self.L.b2hip_get_body_states_of(self.p, len(b), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    # ---- batched teleports and sleep / wake sets on the device (include/b2hip.h, block H: b2hip_set_transforms,
+    # b2hip_set_awakes)
+    def set_transforms(self, bodies, position=None, angle=None):
+        """b2hip_set_transform for each body of `bodies` (ids, each once) in one call on the device: `position` (n, 2) or one
+        pair, `angle` (n,) or one number; what is None keeps its value. The bodies keep their velocities and do not wake."""
+        if position is None and angle is None:
+            raise ValueError("set_transforms: neither a position nor an angle")
+        b = self._body_ids(bodies)
+        n = len(b)
+        pose3 = np.zeros((n, 3), np.float32)
+        if position is not None:
+            p = np.asarray(position, np.float32)
+            p = self._pairs(np.broadcast_to(p, (n, 2)) if p.ndim == 1 and p.shape == (2,) else p, "position")
+            if len(p) != n:
+                raise ValueError("position: %d bodies, %d vectors" % (n, len(p)))
+            pose3[:, :2] = p
+        if angle is not None:
+            a = np.asarray(angle, np.float32)
+            if a.ndim > 1 or (a.ndim == 1 and len(a) != n):
+                raise ValueError("angle: %d bodies, shape %s" % (n, a.shape))
+            pose3[:, 2] = a
+        mask = (1 if position is not None else 0) | (2 if angle is not None else 0)
+        _check(self.L.b2hip_set_transforms(self.p, n, b.ctypes.data_as(C.c_void_p), pose3.ctypes.data_as(C.c_void_p), mask))
+
+    def set_awakes(self, bodies, awake=True):
+        """b2hip_set_awake for each body of `bodies` (ids, each once) in one call on the device: `awake` (n,) or one flag for
+        all. False also zeroes the velocity and the forces of the body."""
+        b = self._body_ids(bodies)
+        n = len(b)
+        flags = np.asarray(awake)
+        if flags.ndim > 1 or (flags.ndim == 1 and len(flags) != n):
+            raise ValueError("awake: %d bodies, shape %s" % (n, flags.shape))
+        flags = np.ascontiguousarray(np.broadcast_to(flags != 0, (n,)), np.uint8)
+        _check(self.L.b2hip_set_awakes(self.p, n, b.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p)))
 
     # ---- batched joints on the device (include/b2hip.h, block G: b2hip_joint_set_motors, b2hip_get_joint_states) and the
     # single-joint reads they are defined by

@@ -30,6 +30,7 @@
  *                                                                           Joints/b2RevoluteJoint.cpp:459-500, b2PrismaticJoint.cpp:549-581
  *   b2hip_destroy_body / _fixture    b2World::DestroyBody, b2Body::DestroyFixture  b2World.cpp:585-670, b2Body.cpp:238-308
  *   b2hip_set_transform / _awake / _bullet, b2hip_apply_*_impulse           b2Body.cpp:451-473, 575-601; b2Body.h:690-718, 885-950
+ *   b2hip_set_transforms / _awakes   b2Body::SetTransform / SetAwake for many bodies in one call (block H)   b2Body.cpp:451-473; b2Body.h:690-718
  *   b2hip_fixture_set_sensor / _thick / _filter, b2hip_fixture_refilter     b2Fixture.cpp:180-257
  *   b2hip_step                       b2World::Step                          b2World.cpp:1613-1710
  *   b2hip_collide                    b2World::Collide / b2ContactManager::Collide      b2World.cpp:1120-1141, b2ContactManager.cpp:177-230
@@ -1112,6 +1113,53 @@ int b2hip_joint_count(const b2hip_world* w);
 int b2hip_joint_is_destroyed(const b2hip_world* w, int joint);
 int b2hip_joint_set_motors(b2hip_world* w, int n, const int32_t* joints, const b2hip_joint_motor* motors, int mask);
 int b2hip_get_joint_states(b2hip_world* w, int n, const int32_t* joints, float inv_dt, b2hip_joint_state* out);
+
+/* ---- H. Batched teleports and sleep / wake sets on the device (csrc/b2hip_api_body_writes.h, csrc/b2d_kernels_body_writes.h) --
+ * Move many bodies between two steps in one call, and put them to sleep or wake them: resetting agents or episodes to their
+ * start poses, moving scripted platforms, respawning debris. b2hip_set_transform edits the host's mirror, waits for the
+ * device and reads 16 bytes back per fixture, and the next step uploads eight rows per body and six small blocking copies
+ * per moved proxy; these calls edit the device's rows, fat AABBs and move buffer in one launch. They are two more write
+ * calls of block F's family and follow its conventions unless stated otherwise.
+ *
+ * Definition by equivalence. Each call has the effect of the existing single-body calls made for i = 0 .. n-1 in order, to
+ * the bit, for everything a caller can observe afterwards: b2hip_get_body_states and b2hip_get_body_states_of,
+ * b2hip_get_fat_aabb(s), batched queries made before the next step, later single-body edits, a snapshot that is loaded and
+ * stepped, every later step's body states and contacts. (The order of the entries in the move buffer is not observable and
+ * may differ: the pairs are sorted.) With s the state b2hip_get_body_states reports for bodies[i] at the call:
+ *   b2hip_set_transforms: b2hip_set_transform(w, b, x', y', a') with x', y' from pose3 when mask bit 0 (value 1) is set, else
+ *                         s.px, s.py, and a' from pose3 when mask bit 1 (value 2) is set, else s.angle.
+ *     Per body: the transform becomes (x', y', sin a', cos a'), the centre c = xf * localCenter, the position row (c, a') with
+ *     the sleep time unchanged, and the sweep origin (c, a'). Nothing else of the body changes: it does not wake, it keeps its
+ *     velocity, and static and kinematic bodies move as well (b2Body.cpp:451-473).
+ *     Per proxy of the body, newest first: the shape's AABB at the new transform; if the fat AABB contains it nothing
+ *     happens; otherwise the fat AABB becomes that box grown by the AABB extension (0.1 m) on each side, with no displacement
+ *     term, and the proxy is appended once to the move buffer. An inactive body has no proxies: its pose is set and no proxy
+ *     row is touched.
+ *   b2hip_set_awakes:     b2hip_set_awake(w, b, awake[i] != 0). False clears the awake flag and zeroes the sleep time, the
+ *     velocity and the force and torque, on any body type. True sets the flag and zeroes the sleep time, except that a static
+ *     body that is awake already is left untouched.
+ * Order: edits made before the call lie underneath it - a body or fixture created since the last step can be named - and edits
+ *   made after it on top of it: a b2hip_set_transform after a batch moves the body again, a b2hip_apply_force after
+ *   b2hip_set_awakes(false) adds to zero. Two calls before one step act one after the other.
+ * bodies: n body ids, each in [0, b2hip_body_count), not destroyed, and each AT MOST ONCE per call.
+ * Refusals, in this order: n outside [0, 2^24], a NULL bodies / pose3 / awake with n > 0, a mask other than 1, 2 or 3:
+ *   B2HIP_ERR_INVALID before the world is looked at. A NULL world, or a call inside an open step (a listener's callback window
+ *   included): B2HIP_ERR_INVALID. A sharded world: B2HIP_ERR_UNSUPPORTED. An id out of range, a destroyed body or an id that
+ *   occurs twice: B2HIP_ERR_INVALID, and b2hip_last_error names the first offender by entry and id. A refused call applies
+ *   nothing. n == 0 is a successful no-op.
+ * The move buffer. It holds 2 x fixtures + 64 entries and is emptied by the step. Neither the reference nor the single call
+ *   removes duplicates from buffered moves, so repeated teleports of the same bodies between two steps can fill it.
+ *   b2hip_set_transforms adds the live proxies of the named bodies - the most the call can append - to the moves the device
+ *   has buffered, and if the sum does not fit it returns B2HIP_ERR_UNSUPPORTED, says to step first, and applies nothing. One
+ *   batch over every body of a freshly stepped world always fits.
+ * Cost: 4 + 12 bytes (transforms) or 4 + 1 bytes (awakes) per entry cross in one copy; one launch edits one body per lane, and
+ *   the call returns when the device is done. b2hip_set_transforms reads the move counter (4 bytes) first; otherwise nothing
+ *   comes back, and the body-state table is not fetched. A lane walks the proxy list of its body: a body with a long list (a
+ *   container, a chain of edges) is walked by one lane, serially. */
+/* pose3: n x (x, y, angle); mask: 1 position, 2 angle, 3 both */
+int b2hip_set_transforms(b2hip_world* w, int n, const int32_t* bodies, const float* pose3, int mask);
+/* awake: one byte per entry, 0 = SetAwake(false), non-zero = SetAwake(true) */
+int b2hip_set_awakes(b2hip_world* w, int n, const int32_t* bodies, const uint8_t* awake);
 
 #ifdef __cplusplus
 }
