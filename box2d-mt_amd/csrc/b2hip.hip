@@ -43,12 +43,16 @@
 // unit that includes them - seven units would be seven device compiles and seven copies of the kernels; the files below are
 // consecutive pieces of what used to be one 6 400-line file and share its scope) ------------------------------------------
 #include "b2hip_host_world.h"
+#include "b2hip_host_upload.h"
 #include "b2hip_host_phases.h"
 #include "b2hip_host_toi.h"
 
 extern "C"
 {
 #include "b2hip_api_world.h"
+#include "b2hip_api_fixtures.h"
+#include "b2hip_api_bodies.h"
+#include "b2hip_api_joints.h"
 #include "b2hip_api_step.h"
 #include "b2hip_api_snapshot.h"
 #include "b2hip_api_sharding.h"

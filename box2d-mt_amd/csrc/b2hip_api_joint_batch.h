@@ -37,7 +37,7 @@ static int jointBatchIds(b2hip_world* w, const char* what, int n, const int32_t*
 		{
 			const int type = w->joints[(size_t)j].type;
 			if (type == B2D_JOINT_DEAD) why = ", which is destroyed";
-			else if (type != B2D_JOINT_REVOLUTE && type != B2D_JOINT_PRISMATIC && type != B2D_JOINT_WHEEL) why = ", whose type has no motor";
+			else if (!jointHasMotor(type)) why = ", whose type has no motor";
 			else if (w->jbSeen[(size_t)j] == w->jbEpoch) why = " a second time";
 			else w->jbSeen[(size_t)j] = w->jbEpoch;
 		}

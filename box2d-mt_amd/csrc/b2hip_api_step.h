@@ -1,6 +1,57 @@
 // b2hip_api_step.h - part of the ONE translation unit b2hip.hip, inside its extern "C" block: b2hip_step and its phase entry
-// points, the end of a step (read-back, late pair update, the listener's records, profile, counters; the TOI phase's part: b2hip_host_toi.h), state / contact event getters.
+// points, the start of a step (stepBeginImpl: the pending edits go up first), the end of a step (read-back, late pair update,
+// the listener's records, profile, counters; the TOI phase's part: b2hip_host_toi.h), state / contact event getters.
 // (No include guard on purpose: b2hip.hip includes it exactly once, in order - the fragments share one scope.)
+
+static int stepBeginImpl(b2hip_world* w, float dt, int velocity_iterations, int position_iterations)
+{
+	int rc = flushEdits(w);
+	if (rc) return rc;
+	StepParams& sp = w->sp;
+	sp.dt = dt;
+	sp.inv_dt = dt > 0.0f ? 1.0f / dt : 0.0f;
+	sp.dtRatio = w->inv_dt0 * dt;
+	sp.velIters = velocity_iterations;
+	sp.posIters = position_iterations;
+	sp.warmStarting = w->def.warm_starting;
+	sp.allowSleep = w->def.allow_sleep;
+	sp.gravity = v2(w->def.gravity_x, w->def.gravity_y);
+	if (w->kernelTiming > 1)
+	{
+		w->ktUsed = 0;
+		w->ktKind = 0;
+	}
+	w->stepActive = true;
+	w->stepSolves = w->stepComplete;
+	w->dw.toiContinue = w->stepComplete ? 0 : 1;
+	w->dw.toiEventCap = w->def.sub_stepping ? 1 : 0;
+	// k_step_begin zeroes the per-step counters (it keeps nContacts / nMoves / cur)
+	// (b2Profile::step: from the start of this kernel to the end of k_end_step, slots 14 and 13)
+	w->dw.stampMask = 1u << 14;
+	LAUNCH(w, k_step_begin, 1, 64, w->dw, w->gridBar.p);
+	w->restArrived = 0; // (bar[5] starts the step at 0)
+	w->toiStep.countersFresh = true;
+	rc = applyPendingFilters(w);
+	if (rc) return rc;
+	rc = applyEditOps(w, false); // (after k_step_begin: the end events of destroyed contacts belong to this step's list)
+	if (rc) return rc;
+	if (w->spatial)
+	{
+		if (listenerOn(w) || hasFilter(w) || w->def.sub_stepping) return setError(B2HIP_ERR_UNSUPPORTED, "contact listeners, filters and sub-stepping are not supported in a spatially sharded world");
+		rc = spBeginStep(w);
+		if (rc) return rc;
+	}
+	stampPhase(w, 0);
+	// b2World.cpp:1628-1639: new fixtures -> find their contacts before colliding
+	if (w->newFixture)
+	{
+		rc = findNewContacts(w, true);
+		if (rc) return rc;
+		w->newFixture = false;
+	}
+	stampPhase(w, 1);
+	return 0;
+}
 
 int b2hip_step_begin(b2hip_world* w, float dt, int velocity_iterations, int position_iterations)
 {

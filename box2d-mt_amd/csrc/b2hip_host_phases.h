@@ -1580,13 +1580,3 @@ static int checkUsable(b2hip_world* w, const char* what, bool mutator)
 	return 0;
 }
 
-static int addJoint(b2hip_world* w, const JointRec& j)
-{
-	if (int rcu = checkUsable(w, "b2hip_create_joint", true)) return rcu;
-	w->joints.push_back(j);
-	if (w->spatial) w->spOwnersDirty = true; // (a joint may join bodies of different owners: resolved at the next step)
-	// b2World::CreateJoint (b2World.cpp:716-732): contacts between the two bodies are re-filtered
-	if (j.collideConnected == 0) w->pendingFilter.push_back(std::make_pair(j.bodyA, j.bodyB));
-	return (int)w->joints.size() - 1;
-}
-
