@@ -211,6 +211,8 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 //     created so far (destroyed ones included: the range of id 28).
 // 28: the bodies of `count` joints from `first`, four ints each: bodyA, bodyB (-1, -1: destroyed), a gear joint's bodyC, bodyD
 //     (else -1, -1). From the host's mirror.
+// 29: one long long: batched destroy / set-active calls since the world was created whose list of contacts with a TOI slot went
+//     through the radix sort (longer than the one-workgroup sort takes; B2HIP_TEST_LIFECYCLE_SORT_MAX lowers that).
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -273,6 +275,12 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 	{
 		if (first != 0 || count != 1) return setError(B2HIP_ERR_INVALID, "narrow-phase statistics: [0, 1)");
 		memcpy(out, &w->statCollideCompact, sizeof(long long));
+		return 0;
+	}
+	case 29:
+	{
+		if (first != 0 || count != 1) return setError(B2HIP_ERR_INVALID, "lifecycle statistics: [0, 1)");
+		memcpy(out, &w->statLifecycleLongSorts, sizeof(long long));
 		return 0;
 	}
 	case 25:

@@ -461,6 +461,7 @@ static int stepEndImpl(b2hip_world* w)
 		}
 	}
 	w->events.clear();
+	if (!w->eventsOn) { w->carriedEventKeys.clear(); w->carriedEventInfo.clear(); }
 	// (the rows were left out of a read-back because another one was due, and it did not come: safety net, never seen)
 	if (w->h_dstate->c.rowsSkipped == 1)
 	{
@@ -475,12 +476,18 @@ static int stepEndImpl(b2hip_world* w)
 		HIP_TRY(hipMemcpyAsync(&nEv, &w->d_state.p->c.nEvents, sizeof(int), hipMemcpyDeviceToHost, w->stream));
 		HIP_TRY(hipStreamSynchronize(w->stream));
 		if (nEv > w->dw.capContacts) return setError(B2HIP_ERR_CAPACITY, "contact event buffer overflow");
+		const int nDev = nEv;
+		nEv += (int)w->carriedEventKeys.size(); // (end events of contacts a batched call destroyed since the last step: b2hip_api_body_lifecycle.h)
 		if (nEv > 0)
 		{
 			std::vector<unsigned long long> keys(nEv);
 			std::vector<int4> info(nEv);
-			HIP_TRY(hipMemcpy(keys.data(), w->evKey.p, nEv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-			HIP_TRY(hipMemcpy(info.data(), w->evInfo.p, nEv * sizeof(int4), hipMemcpyDeviceToHost));
+			if (nDev > 0) HIP_TRY(hipMemcpy(keys.data(), w->evKey.p, nDev * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+			if (nDev > 0) HIP_TRY(hipMemcpy(info.data(), w->evInfo.p, nDev * sizeof(int4), hipMemcpyDeviceToHost));
+			std::copy(w->carriedEventKeys.begin(), w->carriedEventKeys.end(), keys.begin() + nDev);
+			std::copy(w->carriedEventInfo.begin(), w->carriedEventInfo.end(), info.begin() + nDev);
+			w->carriedEventKeys.clear();
+			w->carriedEventInfo.clear();
 			std::vector<int> order(nEv);
 			for (int i = 0; i < nEv; ++i) order[i] = i;
 			// begins before ends, each group by proxy-id pair (b2ContactManager.cpp:420-438, b2ContactPointerLessThan :64-67)
@@ -711,6 +718,8 @@ int b2hip_enable_contact_events(b2hip_world* w, int enable)
 	w->eventsOn = enable != 0;
 	w->dw.eventsOn = w->eventsOn ? 1 : 0;
 	w->events.clear();
+	w->carriedEventKeys.clear();
+	w->carriedEventInfo.clear();
 	return B2HIP_OK;
 }
 

@@ -382,16 +382,12 @@ static int applyPendingFilters(b2hip_world* w)
 static int downloadState(b2hip_world* w, int clearForces, bool skipRowsIfRedo = false);
 static int startEarlyRows(b2hip_world* w);
 
-static int applyEditOps(b2hip_world* w, bool betweenSteps)
+// What follows the ops on the stream: the compaction of the contact array if contacts were destroyed, and the device state
+// back. (The batched destruction and activation sets, b2hip_api_body_lifecycle.h, mark their contacts themselves and end here too.)
+static int editOpsTail(b2hip_world* w, bool destroys, bool betweenSteps)
 {
-	if (w->editOps.empty()) return 0;
-	bool destroys = false;
-	for (size_t k = 0; k < w->editOps.size(); ++k) destroys = destroys || w->editOps[k].x == EDIT_DESTROY_BODY || w->editOps[k].x == EDIT_DESTROY_FIXTURE;
-	int rc = w->d_editOps.ensure(w->editOps.size(), w->stream, false, false);
-	if (rc) return rc;
-	HIP_TRY(hipMemcpyAsync(w->d_editOps.p, w->editOps.data(), w->editOps.size() * sizeof(int2), hipMemcpyHostToDevice, w->stream));
 	DW& d = w->dw;
-	LAUNCH(w, k_apply_edits, 1, 1024, d, (const int2*)w->d_editOps.p, (int)w->editOps.size());
+	int rc = 0;
 	if (destroys)
 	{
 		LAUNCH(w, k_edit_keepflags, gridFor(d.capContacts), 256, d);
@@ -410,9 +406,24 @@ static int applyEditOps(b2hip_world* w, bool betweenSteps)
 	}
 	rc = readState(w); // (also makes the staging vector reusable, and the state rows above readable)
 	if (rc) return rc;
-	w->editOps.clear();
 	w->contactsKnown = true; // (read back behind everything that was queued)
 	w->lastContacts = w->h_dstate->c.nContacts;
 	w->last.nContacts = w->lastContacts;
+	return 0;
+}
+
+static int applyEditOps(b2hip_world* w, bool betweenSteps)
+{
+	if (w->editOps.empty()) return 0;
+	bool destroys = false;
+	for (size_t k = 0; k < w->editOps.size(); ++k) destroys = destroys || w->editOps[k].x == EDIT_DESTROY_BODY || w->editOps[k].x == EDIT_DESTROY_FIXTURE;
+	int rc = w->d_editOps.ensure(w->editOps.size(), w->stream, false, false);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(w->d_editOps.p, w->editOps.data(), w->editOps.size() * sizeof(int2), hipMemcpyHostToDevice, w->stream));
+	DW& d = w->dw;
+	LAUNCH(w, k_apply_edits, 1, 1024, d, (const int2*)w->d_editOps.p, (int)w->editOps.size());
+	rc = editOpsTail(w, destroys, betweenSteps);
+	if (rc) return rc;
+	w->editOps.clear();
 	return 0;
 }

@@ -276,6 +276,16 @@ struct b2hip_world
 	DevArray<float4> bwIn;
 	DevArray<float2> bwRows;
 	size_t forceDevCount = 0;
+	// batched destruction and activation sets (b2hip_api_body_lifecycle.h): lcNamed a word per body, entry + 1 while a call runs
+	// and 0 between calls; lcWords[0] the length of the call's list of contacts with a TOI slot (the list itself borrows the
+	// pair update's key buffer); lifecycleSortMax: lists up to this long are sorted by one workgroup in LDS
+	// (B2HIP_TEST_LIFECYCLE_SORT_MAX: fewer, so that a small world takes the radix sort); carriedEvent*: end events of contacts a
+	// batch destroyed, delivered with the next step's
+	DevArray<int> lcNamed, lcWords;
+	int lifecycleSortMax = LIFECYCLE_SORT_MAX;
+	long long statLifecycleLongSorts = 0;
+	std::vector<unsigned long long> carriedEventKeys;
+	std::vector<int4> carriedEventInfo;
 	// batched joints (b2hip_api_joint_batch.h): the gathered joint states on the device (the ids share bcIds, the motor edits
 	// bwIn); jbSeen / jbEpoch: the host's duplicate check of a write call's joint ids
 	DevArray<float4> jbOut;
@@ -968,6 +978,7 @@ static void readSwitches(b2hip_world* w)
 	w->collideSplitEnv = envInt("B2HIP_COLLIDE_SPLIT", -1);
 	w->collideCompactOn = envInt("B2HIP_COLLIDE_COMPACT", 1) != 0;
 	w->collideChunk = std::min(std::max(envInt("B2HIP_TEST_COLLIDE_CHUNK", 256), 1), 256);
+	w->lifecycleSortMax = std::min(std::max(envInt("B2HIP_TEST_LIFECYCLE_SORT_MAX", LIFECYCLE_SORT_MAX), 0), LIFECYCLE_SORT_MAX);
 	w->collideUniOff = envInt("B2HIP_COLLIDE_UNI", 1) == 0;
 	w->collideSortEnv = envInt("B2HIP_COLLIDE_SORT", -1);
 	w->sortOnepass = envInt("B2HIP_SORT_ONEPASS", 1) != 0;

@@ -237,6 +237,9 @@ def _configure(L, optional_ok=False):
         "b2hip_set_transform": [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float],
         "b2hip_set_transforms": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
         "b2hip_set_awakes": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_set_active": [C.c_void_p, C.c_int, C.c_int],
+        "b2hip_destroy_bodies": [C.c_void_p, C.c_int, C.c_void_p],
+        "b2hip_set_actives": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_get_joint_reaction": [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)],
         "b2hip_get_joint_limit_state": [C.c_void_p, C.c_int],
         "b2hip_joint_count": [C.c_void_p],
@@ -498,6 +501,10 @@ class World:
 
     def set_awake(self, body, flag=True):
         _check(self.L.b2hip_set_awake(self.p, body, int(flag)))
+
+    def set_active(self, body, flag=True):
+        """b2Body::SetActive: an inactive body keeps its fixtures and its state, and has no proxies and no contacts."""
+        _check(self.L.b2hip_set_active(self.p, body, int(flag)))
 
     def set_transform(self, body, position, angle):
         """b2Body::SetTransform: the body's origin and angle; it keeps its velocity and does not wake."""
@@ -890,6 +897,25 @@ class World:
             raise ValueError("awake: %d bodies, shape %s" % (n, flags.shape))
         flags = np.ascontiguousarray(np.broadcast_to(flags != 0, (n,)), np.uint8)
         _check(self.L.b2hip_set_awakes(self.p, n, b.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p)))
+
+    # ---- batched destruction and activation sets on the device (include/b2hip.h, block I: b2hip_destroy_bodies,
+    # b2hip_set_actives)
+    def destroy_bodies(self, bodies):
+        """b2hip_destroy_body for each body of `bodies` (ids, each once) in one call on the device: the bodies, their fixtures
+        and their contacts (ids are never reused). A batch that names a body with a live joint runs the single calls."""
+        b = self._body_ids(bodies)
+        _check(self.L.b2hip_destroy_bodies(self.p, len(b), b.ctypes.data_as(C.c_void_p)))
+
+    def set_actives(self, bodies, active=True):
+        """b2hip_set_active for each body of `bodies` (ids, each once) in one call on the device: `active` (n,) or one flag
+        for all. A body that has the requested state already is left alone."""
+        b = self._body_ids(bodies)
+        n = len(b)
+        flags = np.asarray(active)
+        if flags.ndim > 1 or (flags.ndim == 1 and len(flags) != n):
+            raise ValueError("active: %d bodies, shape %s" % (n, flags.shape))
+        flags = np.ascontiguousarray(np.broadcast_to(flags != 0, (n,)), np.uint8)
+        _check(self.L.b2hip_set_actives(self.p, n, b.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p)))
 
     # ---- batched joints on the device (include/b2hip.h, block G: b2hip_joint_set_motors, b2hip_get_joint_states) and the
     # single-joint reads they are defined by

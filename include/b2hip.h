@@ -31,6 +31,7 @@
  *   b2hip_destroy_body / _fixture    b2World::DestroyBody, b2Body::DestroyFixture  b2World.cpp:585-670, b2Body.cpp:238-308
  *   b2hip_set_transform / _awake / _bullet, b2hip_apply_*_impulse           b2Body.cpp:451-473, 575-601; b2Body.h:690-718, 885-950
  *   b2hip_set_transforms / _awakes   b2Body::SetTransform / SetAwake for many bodies in one call (block H)   b2Body.cpp:451-473; b2Body.h:690-718
+ *   b2hip_destroy_bodies / b2hip_set_actives   b2World::DestroyBody / b2Body::SetActive for many bodies in one call (block I)   b2World.cpp:585-670; b2Body.cpp:496-544
  *   b2hip_fixture_set_sensor / _thick / _filter, b2hip_fixture_refilter     b2Fixture.cpp:180-257
  *   b2hip_step                       b2World::Step                          b2World.cpp:1613-1710
  *   b2hip_collide                    b2World::Collide / b2ContactManager::Collide      b2World.cpp:1120-1141, b2ContactManager.cpp:177-230
@@ -1160,6 +1161,67 @@ int b2hip_get_joint_states(b2hip_world* w, int n, const int32_t* joints, float i
 int b2hip_set_transforms(b2hip_world* w, int n, const int32_t* bodies, const float* pose3, int mask);
 /* awake: one byte per entry, 0 = SetAwake(false), non-zero = SetAwake(true) */
 int b2hip_set_awakes(b2hip_world* w, int n, const int32_t* bodies, const uint8_t* awake);
+
+/* ---- I. Batched destruction and activation sets on the device (csrc/b2hip_api_body_lifecycle.h, csrc/b2d_kernels_body_lifecycle.h)
+ * Retire many bodies for good, or switch them off and on again, between two steps in one call: debris that has left the
+ * scene, projectiles that have hit, a pool of bodies that respawn. Body ids are never reused - a destroyed body is a dead slot
+ * for the life of the world - so pooling with b2hip_set_actives is the way to respawn, and b2hip_destroy_bodies the way to
+ * retire. The single calls queue one contact-array operation per body, each of which is a walk of ONE workgroup over the whole
+ * contact array, and five small blocking copies per fixture; these calls edit the rows and the proxies in one launch each and
+ * destroy the contacts of the whole set in one grid-wide pass. They are two more write calls of block F's family and follow
+ * the conventions of b2hip_set_transforms unless stated otherwise.
+ *
+ * Definition by equivalence. A call has the effect of b2hip_destroy_body(w, bodies[i]), respectively
+ * b2hip_set_active(w, bodies[i], active[i] != 0), made for i = 0 .. n-1 in order with nothing in between, to the bit, for
+ * everything a caller can observe afterwards: b2hip_get_body_states / _of (the rows of dead bodies included),
+ * b2hip_body_is_destroyed / b2hip_fixture_is_destroyed and the counts, b2hip_get_fat_aabb(s) of live proxies,
+ * b2hip_get_contacts before and after later steps (contacts appear in proxy-id order), the contact events of the next step,
+ * batched queries made before the next step, later single-body edits, a snapshot that is saved (and, where the world holds
+ * no inactive body, loaded and stepped), every later step. (The order of the entries in the move buffer and of the events
+ * appended within one call is not observable.) An entry of b2hip_set_actives that has the requested state already is a
+ * no-op, as the single call is. b2hip_set_actives touches no joint, as the single call does not.
+ * When the contacts go. The single calls queue the destruction of the contacts for the next step or the next reader of the
+ *   contacts (b2hip_get_contacts, b2hip_contact_count, a batched call): until then b2hip_get_body_states does not show the
+ *   bodies that the destroyed touching contacts wake. A batch destroys them before it returns (the loop it runs for a jointed
+ *   body included: what the loop queued is applied before the call returns). Compare the two routes behind a read of the
+ *   contacts. The end events of the destroyed contacts are delivered with the next step's events on either route.
+ * Order: edits made before the call lie underneath it: they go to the device first, queued contact operations included - a
+ *   body created since the last step can be named - and edits made after it on top of it. Two calls before one step act one
+ *   after the other. This LIMITS the definition by equivalence to the call itself: single calls made before a batch, or two
+ *   batches, are not the same as all their single calls queued together. Queued together, every body's rows are uploaded before
+ *   any contact goes, so a body that an earlier call's destroyed contacts wake and a later call destroys or puts to sleep can
+ *   end with another awake bit. A caller who mixes the routes gets the batch's order - each call complete before the next -
+ *   which is what the single route gives with a read of the contacts (b2hip_contact_count) between the calls. The end events
+ *   of single calls that a batch applies this way are delivered with the next step's, like the batch's own.
+ * Joints. b2hip_destroy_body destroys the live joints of its body first, and b2hip_destroy_joint wakes both bodies in an order
+ *   against the other entries' edits that can be observed. If any named body carries a live joint (a gear joint's third and
+ *   fourth body count), b2hip_destroy_bodies runs the loop of b2hip_destroy_body itself for the whole batch - pending edits
+ *   to the device first, and what the loop queued applied before the call returns, as on the batched route: the result is
+ *   the same, the cost is the loop's.
+ * bodies: n body ids, each in [0, b2hip_body_count), not destroyed, and each AT MOST ONCE per call.
+ * Refusals, in this order: n outside [0, 2^24], a NULL bodies / active with n > 0: B2HIP_ERR_INVALID before the world is looked
+ *   at. A NULL, failed or mid-step world (a listener's callback window included): B2HIP_ERR_INVALID. A sharded world:
+ *   B2HIP_ERR_UNSUPPORTED. An id out of range, a destroyed body or an id that occurs twice: B2HIP_ERR_INVALID, and
+ *   b2hip_last_error names the first offender by entry and id. A refused call applies nothing. n == 0 is a successful no-op.
+ *   A B2HIP_ERR_HIP from these calls is no refusal: a copy, a launch or a sort failed behind the host's bookkeeping, the device
+ *   is partly edited, and the world is marked failed - every later call says so, and it can only be inspected and destroyed.
+ * Two refusals more, of b2hip_set_actives, both checked before anything is written:
+ *   The move buffer. An activated proxy buffers a move. The call adds the proxies it would create to the moves the device has
+ *     buffered, and if the sum does not fit (2 x fixtures + 64 entries, emptied by the step) it returns B2HIP_ERR_UNSUPPORTED,
+ *     says to step first, and applies nothing.
+ *   Proxy-id reuse. The ids the reference's tree would hand out are replayed in entry order on a copy of the allocator first.
+ *     Where an internal node's id would become a leaf's (the broad-phase tree was emptied and refilled: not modelled) the call
+ *     returns B2HIP_ERR_UNSUPPORTED, names the entry, and leaves the world untouched. This is the ONE place where a refused
+ *     batch differs from a refused loop: b2hip_set_active returns the same code from the middle of its loop, with the earlier
+ *     fixtures of that body - and the earlier bodies of the loop - already edited.
+ * Cost: 4 + 4 bytes per entry and 16 bytes per fixture of a named body cross in one copy; the device's counters (about 2 KB)
+ *   come back first. One pass over the contact array destroys the contacts of all named bodies; the contacts among them that
+ *   hold a slot of the continuous-collision partition are given back by one lane in the loop's order, after a sort (a world
+ *   without continuous collision has none). The contact array is compacted and the body-state table read back, as behind the
+ *   single calls; a batch of b2hip_set_actives that only activates does neither. */
+int b2hip_destroy_bodies(b2hip_world* w, int n, const int32_t* bodies);
+/* active: one byte per entry, 0 = SetActive(false), non-zero = SetActive(true) */
+int b2hip_set_actives(b2hip_world* w, int n, const int32_t* bodies, const uint8_t* active);
 
 #ifdef __cplusplus
 }
