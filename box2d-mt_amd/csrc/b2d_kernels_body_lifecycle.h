@@ -209,13 +209,11 @@ __device__ inline void lifecycleToiReplay(const DW& W, const unsigned long long*
 	S->c.nToiOrder = nToi;
 }
 
-// The list while it fits LDS: a bitonic sort by one workgroup, then the replay. (A longer list: the host sorts it with the
-// pair update's radix sort and launches k_lifecycle_toi_replay.)
-__global__ __launch_bounds__(1024) void k_lifecycle_toi_sort_replay(DW W, unsigned long long* keys, const int* toiCount)
+// `count` keys (0 < count <= LIFECYCLE_SORT_MAX, uniform) into s_keys, ascending: a bitonic sort by one workgroup of 1024.
+// (The batched fixture sets, b2d_kernels_fixture_batch.h, sort their list with it too.)
+__device__ inline void lifecycleSortInLds(unsigned long long* s_keys, const unsigned long long* keys, int count)
 {
-	__shared__ unsigned long long s_keys[LIFECYCLE_SORT_MAX];
-	const int count = *toiCount, t = (int)threadIdx.x;
-	if (count <= 0 || count > LIFECYCLE_SORT_MAX) return; // (uniform)
+	const int t = (int)threadIdx.x;
 	int room = 64;
 	while (room < count) room <<= 1;
 	for (int k = t; k < room; k += 1024) s_keys[k] = k < count ? keys[k] : ~0ull;
@@ -237,7 +235,17 @@ __global__ __launch_bounds__(1024) void k_lifecycle_toi_sort_replay(DW W, unsign
 			__syncthreads();
 		}
 	}
-	if (t == 0) lifecycleToiReplay(W, s_keys, count);
+}
+
+// The list while it fits LDS: sorted by one workgroup, then the replay. (A longer list: the host sorts it with the pair
+// update's radix sort and launches k_lifecycle_toi_replay.)
+__global__ __launch_bounds__(1024) void k_lifecycle_toi_sort_replay(DW W, unsigned long long* keys, const int* toiCount)
+{
+	__shared__ unsigned long long s_keys[LIFECYCLE_SORT_MAX];
+	const int count = *toiCount;
+	if (count <= 0 || count > LIFECYCLE_SORT_MAX) return; // (uniform)
+	lifecycleSortInLds(s_keys, keys, count);
+	if (threadIdx.x == 0) lifecycleToiReplay(W, s_keys, count);
 }
 
 __global__ void k_lifecycle_toi_replay(DW W, const unsigned long long* sortedKeys, const int* toiCount, int toiCap)

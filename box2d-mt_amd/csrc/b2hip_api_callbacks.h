@@ -213,6 +213,9 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 //     (else -1, -1). From the host's mirror.
 // 29: one long long: batched destroy / set-active calls since the world was created whose list of contacts with a TOI slot went
 //     through the radix sort (longer than the one-workgroup sort takes; B2HIP_TEST_LIFECYCLE_SORT_MAX lowers that).
+// 30: two long longs: batched b2hip_fixture_set_sensors / _thicks calls since the world was created [0] whose list of contacts
+//     with a changed TOI candidacy went through the radix sort (the same threshold and hook), [1] that listed a second time
+//     because the first listing's room was short (B2HIP_TEST_FIXTURE_LIST_ROOM lowers that room).
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -281,6 +284,13 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 	{
 		if (first != 0 || count != 1) return setError(B2HIP_ERR_INVALID, "lifecycle statistics: [0, 1)");
 		memcpy(out, &w->statLifecycleLongSorts, sizeof(long long));
+		return 0;
+	}
+	case 30:
+	{
+		const long long stats[2] = { w->statFixtureLongSorts, w->statFixtureRelists };
+		if (first < 0 || count < 0 || first + count > 2) return setError(B2HIP_ERR_INVALID, "fixture-batch statistics: [0, 2)");
+		memcpy(out, stats + first, (size_t)count * sizeof(long long));
 		return 0;
 	}
 	case 25:

@@ -252,7 +252,7 @@ void b2hip_world_destroy(b2hip_world* w)
 	w->qScanWords.release(); w->qWords.release(); w->qHits.release(); w->qDistances.release(); w->qPoses.release(); w->qShapes.release();
 	w->qKeys.release(); w->qKeysWork.release(); w->qAny.release();
 	w->bcSlot.release(); w->bcIds.release(); w->bcCounts.release(); w->bcRecords.release(); w->bcTotals.release();
-	w->bwIn.release(); w->bwRows.release(); w->jbOut.release(); w->lcNamed.release(); w->lcWords.release();
+	w->bwIn.release(); w->bwRows.release(); w->jbOut.release(); w->lcNamed.release(); w->lcWords.release(); w->fxNamed.release();
 	if (w->qPinned) (void)hipHostFree(w->qPinned);
 	if (w->h_state) (void)hipHostFree(w->h_state);
 	if (w->h_dstate) (void)hipHostFree(w->h_dstate);

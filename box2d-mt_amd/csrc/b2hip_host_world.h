@@ -286,6 +286,15 @@ struct b2hip_world
 	long long statLifecycleLongSorts = 0;
 	std::vector<unsigned long long> carriedEventKeys;
 	std::vector<int4> carriedEventInfo;
+	// batched fixture sets (b2hip_api_fixture_batch.h): fxNamed a word per fixture, entry + 1 while a call runs and 0 between
+	// calls (the ids share bcIds, the records bwIn, the list's length lcWords[0], its sort lifecycleSortMax); fbSeen / fbEpoch: the
+	// host's duplicate check; fixtureListRoom: room the first listing of a call gets (B2HIP_TEST_FIXTURE_LIST_ROOM; -1: all the
+	// pair buffer has), so that a small world lists twice; the statistics of b2hip_debug_read 30
+	DevArray<int> fxNamed;
+	std::vector<uint32_t> fbSeen;
+	uint32_t fbEpoch = 0;
+	int fixtureListRoom = -1;
+	long long statFixtureLongSorts = 0, statFixtureRelists = 0;
 	// batched joints (b2hip_api_joint_batch.h): the gathered joint states on the device (the ids share bcIds, the motor edits
 	// bwIn); jbSeen / jbEpoch: the host's duplicate check of a write call's joint ids
 	DevArray<float4> jbOut;
@@ -979,6 +988,7 @@ static void readSwitches(b2hip_world* w)
 	w->collideCompactOn = envInt("B2HIP_COLLIDE_COMPACT", 1) != 0;
 	w->collideChunk = std::min(std::max(envInt("B2HIP_TEST_COLLIDE_CHUNK", 256), 1), 256);
 	w->lifecycleSortMax = std::min(std::max(envInt("B2HIP_TEST_LIFECYCLE_SORT_MAX", LIFECYCLE_SORT_MAX), 0), LIFECYCLE_SORT_MAX);
+	w->fixtureListRoom = std::max(envInt("B2HIP_TEST_FIXTURE_LIST_ROOM", -1), -1);
 	w->collideUniOff = envInt("B2HIP_COLLIDE_UNI", 1) == 0;
 	w->collideSortEnv = envInt("B2HIP_COLLIDE_SORT", -1);
 	w->sortOnepass = envInt("B2HIP_SORT_ONEPASS", 1) != 0;

@@ -149,6 +149,9 @@ JOINT_MOTOR_DTYPE = np.dtype([("enable_motor", "i4"), ("motor_speed", "f4"), ("m
 JOINT_STATE_DTYPE = np.dtype([("type", "i4"), ("limit_state", "i4"), ("coordinate", "f4"), ("speed", "f4"), ("coordinate2", "f4"),
                               ("speed2", "f4"), ("force", "f4", 2), ("torque", "f4"), ("motor", "f4"), ("pad", "f4", 2)])
 JOINT_MOTOR_ENABLE, JOINT_MOTOR_SPEED, JOINT_MOTOR_MAX = 1, 2, 4  # the mask bits of b2hip_joint_set_motors
+FIXTURE_FILTER_DTYPE = np.dtype([("category_bits", "u2"), ("mask_bits", "u2"), ("group_index", "i2"), ("pad", "u2")])
+FIXTURE_MATERIAL_DTYPE = np.dtype([("density", "f4"), ("friction", "f4"), ("restitution", "f4")])
+MATERIAL_DENSITY, MATERIAL_FRICTION, MATERIAL_RESTITUTION = 1, 2, 4  # the mask bits of b2hip_fixture_set_materials
 
 _lib = None
 
@@ -240,6 +243,12 @@ def _configure(L, optional_ok=False):
         "b2hip_set_active": [C.c_void_p, C.c_int, C.c_int],
         "b2hip_destroy_bodies": [C.c_void_p, C.c_int, C.c_void_p],
         "b2hip_set_actives": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_fixture_set_thick": [C.c_void_p, C.c_int, C.c_int],
+        "b2hip_fixture_set_filter": [C.c_void_p, C.c_int, C.c_uint16, C.c_uint16, C.c_int16],
+        "b2hip_fixture_set_filters": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_fixture_set_sensors": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_fixture_set_thicks": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_fixture_set_materials": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
         "b2hip_get_joint_reaction": [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)],
         "b2hip_get_joint_limit_state": [C.c_void_p, C.c_int],
         "b2hip_joint_count": [C.c_void_p],
@@ -515,6 +524,17 @@ class World:
 
     def fixture_refilter(self, fixture):
         _check(self.L.b2hip_fixture_refilter(self.p, fixture))
+
+    def fixture_set_filter(self, fixture, category_bits, mask_bits, group_index=0):
+        """b2Fixture::SetFilterData: the new filter, and the fixture's contacts re-filtered at the next step."""
+        _check(self.L.b2hip_fixture_set_filter(self.p, fixture, category_bits, mask_bits, group_index))
+
+    def fixture_set_thick(self, fixture, flag=True):
+        _check(self.L.b2hip_fixture_set_thick(self.p, fixture, int(flag)))
+
+    def fixture_set_material(self, fixture, density, friction, restitution):
+        """b2Fixture::SetDensity / SetFriction / SetRestitution: for the next mass computation / the contacts created from now on."""
+        _check(self.L.b2hip_fixture_set_material(self.p, fixture, density, friction, restitution))
 
     def joint_set_target(self, joint, target):
         _check(self.L.b2hip_joint_set_target(self.p, joint, target[0], target[1]))
@@ -916,6 +936,65 @@ class World:
             raise ValueError("active: %d bodies, shape %s" % (n, flags.shape))
         flags = np.ascontiguousarray(np.broadcast_to(flags != 0, (n,)), np.uint8)
         _check(self.L.b2hip_set_actives(self.p, n, b.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p)))
+
+    # ---- batched fixture sets on the device (include/b2hip.h, block J: b2hip_fixture_set_filters, b2hip_fixture_set_sensors,
+    # b2hip_fixture_set_thicks, b2hip_fixture_set_materials)
+    @staticmethod
+    def _fixture_ids(fixtures):
+        f = np.ascontiguousarray(fixtures, np.int32)
+        if f.ndim != 1:
+            raise ValueError("fixtures: an (n,) array of fixture ids is expected, got shape %s" % (f.shape,))
+        return f
+
+    @staticmethod
+    def _per_fixture(value, n, dtype, name):
+        """`value` as n entries of `dtype`: (n,) or one for all"""
+        v = np.asarray(value)
+        if v.ndim > 1 or (v.ndim == 1 and len(v) != n):
+            raise ValueError("%s: %d fixtures, shape %s" % (name, n, v.shape))
+        return np.broadcast_to(v, (n,)).astype(dtype)
+
+    def fixture_set_filters(self, fixtures, category_bits, mask_bits, group_index=0):
+        """b2hip_fixture_set_filter for each fixture of `fixtures` (ids, each once) in one call on the device: the three filter
+        words (n,) or one for all. Every named fixture is re-filtered, as by the single call."""
+        f = self._fixture_ids(fixtures)
+        n = len(f)
+        rec = np.zeros(n, FIXTURE_FILTER_DTYPE)
+        rec["category_bits"] = self._per_fixture(category_bits, n, np.uint16, "category_bits")
+        rec["mask_bits"] = self._per_fixture(mask_bits, n, np.uint16, "mask_bits")
+        rec["group_index"] = self._per_fixture(group_index, n, np.int16, "group_index")
+        _check(self.L.b2hip_fixture_set_filters(self.p, n, f.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p)))
+
+    def _fixture_flags(self, fn, fixtures, flag, name):
+        f = self._fixture_ids(fixtures)
+        flags = np.ascontiguousarray(self._per_fixture(np.asarray(flag) != 0, len(f), np.uint8, name))
+        _check(getattr(self.L, fn)(self.p, len(f), f.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p)))
+
+    def fixture_set_sensors(self, fixtures, flag=True):
+        """b2hip_fixture_set_sensor for each fixture of `fixtures` (ids, each once) in one call on the device: `flag` (n,) or one
+        for all. The body of a fixture that changes wakes; one that has the requested value already is left alone."""
+        self._fixture_flags("b2hip_fixture_set_sensors", fixtures, flag, "flag")
+
+    def fixture_set_thicks(self, fixtures, flag=True):
+        """b2hip_fixture_set_thick for each fixture of `fixtures` (ids, each once) in one call on the device: `flag` (n,) or one
+        for all."""
+        self._fixture_flags("b2hip_fixture_set_thicks", fixtures, flag, "flag")
+
+    def fixture_set_materials(self, fixtures, density=None, friction=None, restitution=None):
+        """b2hip_fixture_set_material for each fixture of `fixtures` (ids, each once) in one call on the device: each of the
+        three (n,) or one number for all; what is None keeps its value."""
+        f = self._fixture_ids(fixtures)
+        n = len(f)
+        rec = np.zeros(n, FIXTURE_MATERIAL_DTYPE)
+        mask = 0
+        for bit, name, value in ((MATERIAL_DENSITY, "density", density), (MATERIAL_FRICTION, "friction", friction),
+                                 (MATERIAL_RESTITUTION, "restitution", restitution)):
+            if value is not None:
+                rec[name] = self._per_fixture(value, n, np.float32, name)
+                mask |= bit
+        if mask == 0:
+            raise ValueError("fixture_set_materials: neither a density nor a friction nor a restitution")
+        _check(self.L.b2hip_fixture_set_materials(self.p, n, f.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p), mask))
 
     # ---- batched joints on the device (include/b2hip.h, block G: b2hip_joint_set_motors, b2hip_get_joint_states) and the
     # single-joint reads they are defined by

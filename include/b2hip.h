@@ -33,6 +33,7 @@
  *   b2hip_set_transforms / _awakes   b2Body::SetTransform / SetAwake for many bodies in one call (block H)   b2Body.cpp:451-473; b2Body.h:690-718
  *   b2hip_destroy_bodies / b2hip_set_actives   b2World::DestroyBody / b2Body::SetActive for many bodies in one call (block I)   b2World.cpp:585-670; b2Body.cpp:496-544
  *   b2hip_fixture_set_sensor / _thick / _filter, b2hip_fixture_refilter     b2Fixture.cpp:180-257
+ *   b2hip_fixture_set_filters / _sensors / _thicks / _materials   b2Fixture::SetFilterData / SetSensor / SetThickShape / SetFriction ... for many fixtures in one call (block J)   b2Fixture.cpp:180-257; b2Fixture.h:306-334
  *   b2hip_step                       b2World::Step                          b2World.cpp:1613-1710
  *   b2hip_collide                    b2World::Collide / b2ContactManager::Collide      b2World.cpp:1120-1141, b2ContactManager.cpp:177-230
  *   b2hip_solve                      b2World::Solve (islands + b2Island::Solve)        b2World.cpp:1166-1431, b2Island.cpp:184-396
@@ -1222,6 +1223,82 @@ int b2hip_set_awakes(b2hip_world* w, int n, const int32_t* bodies, const uint8_t
 int b2hip_destroy_bodies(b2hip_world* w, int n, const int32_t* bodies);
 /* active: one byte per entry, 0 = SetActive(false), non-zero = SetActive(true) */
 int b2hip_set_actives(b2hip_world* w, int n, const int32_t* bodies, const uint8_t* active);
+
+/* ---- J. Batched fixture sets on the device (csrc/b2hip_api_fixture_batch.h, csrc/b2d_kernels_fixture_batch.h) ------------------
+ * Change what many fixtures collide with, whether they are sensors or thick shapes, and their surface between two steps in
+ * one call: a team goes ghost, debris stops colliding with debris, triggers are armed, a patch of ground turns to ice. The
+ * single calls queue five small blocking copies per fixture for the next step, b2hip_fixture_set_filter / _sensor / _thick
+ * also one or two contact-array operations per fixture, each of which is a walk of ONE workgroup over the whole contact
+ * array, and b2hip_fixture_set_sensor wakes the body through the host's mirror (eight rows uploaded); these calls write the
+ * proxies' words in one launch and visit the contact array once per call. They are four more write calls of block F's family
+ * and follow the conventions of blocks H and I unless stated otherwise.
+ *
+ * Definition by equivalence. A call has the effect of the single call made for i = 0 .. n-1 in order with nothing in between:
+ *   b2hip_fixture_set_filters:   b2hip_fixture_set_filter(w, fixtures[i], filters[i].category_bits, filters[i].mask_bits,
+ *                                filters[i].group_index)
+ *   b2hip_fixture_set_sensors:   b2hip_fixture_set_sensor(w, fixtures[i], sensor[i] != 0)
+ *   b2hip_fixture_set_thicks:    b2hip_fixture_set_thick(w, fixtures[i], thick[i] != 0)
+ *   b2hip_fixture_set_materials: b2hip_fixture_set_material(w, fixtures[i], density, friction, restitution) with each of the
+ *                                three taken from materials[i] when its bit of `mask` is set, else the value the fixture has now
+ * to the bit, for everything a caller can observe afterwards: b2hip_get_body_states / _of with awake bits and sleep times,
+ * b2hip_get_contacts before and after later steps, the contact events of the next steps, b2hip_get_fat_aabb(s), batched
+ * queries made before the next step (their filters read the proxies' words), a snapshot that is saved (it carries the
+ * continuous-collision partition and the buffered moves), later single-fixture calls on the same fixtures, every later step
+ * with continuous collision on.
+ *   A sensor or thick entry that has the requested value already is a no-op, as the single call is: no wake, no contact is
+ *   looked at. A filter entry always re-filters, as the single call does: every contact of the fixture is flagged for the next
+ *   step's filter - a user contact filter (b2hip_set_contact_filter) is asked about it - and the proxy of a fixture whose body
+ *   is active is buffered as moved, so that pairs the new filter admits can form. b2hip_fixture_set_sensors wakes the body of
+ *   every entry that CHANGES (awake bit set, sleep time zero; a static body that is awake already is left untouched);
+ *   b2hip_fixture_set_thicks wakes nobody. Sensors and thick shapes decide which contacts are candidates for continuous
+ *   collision: the slots of that partition are appended and given back in the order the loop of single calls would have
+ *   taken - by entry, within an entry newest contact first. b2hip_fixture_set_materials writes the proxies' friction and
+ *   restitution for the contacts created from now on; existing contacts keep their mixture, and the density is read by the
+ *   next mass computation only (no b2Body::ResetMassData is implied), as with the single call.
+ * Order: edits made before the call lie underneath it: they go to the device first, queued contact operations of single calls
+ *   included (block I says what that means for single calls mixed with batches), and edits made after it on top of it. Two
+ *   calls before one step act one after the other.
+ * fixtures: n fixture ids, each in [0, b2hip_fixture_count), not destroyed, and each AT MOST ONCE per call. A fixture of an
+ *   inactive body can be named (it has no proxy: nothing is buffered for it).
+ * Refusals, in this order: n outside [0, 2^24], a NULL fixtures / filters / sensor / thick / materials with n > 0:
+ *   B2HIP_ERR_INVALID before the world is looked at. A NULL, failed or mid-step world (a listener's callback window
+ *   included): B2HIP_ERR_INVALID. A sharded world: B2HIP_ERR_UNSUPPORTED. A mask that is 0 or has a bit beyond the three
+ *   B2HIP_MATERIAL_* bits; an id out of range, a destroyed fixture or an id that occurs twice: B2HIP_ERR_INVALID, and
+ *   b2hip_last_error names the first offender by entry and id. A refused call applies nothing. n == 0 is a successful no-op.
+ *   A B2HIP_ERR_HIP from these calls is no refusal: a copy, a launch or a sort failed behind the host's bookkeeping, the device
+ *   is partly edited, and the world is marked failed - every later call says so, and it can only be inspected and destroyed.
+ * One refusal more, of b2hip_fixture_set_filters, checked before anything is written:
+ *   The move buffer. The call adds its entries whose body is active to the moves the device has buffered, and if the sum does
+ *     not fit (2 x fixtures + 64 entries, emptied by the step) it returns B2HIP_ERR_UNSUPPORTED, says to step first, and applies
+ *     nothing. One batch over every fixture of a freshly stepped world always fits.
+ * Cost: 4 + 16 bytes per entry cross in one copy; the device's counters (about 2 KB) come back first, and again at the end of
+ *   every call but b2hip_fixture_set_materials, which launches once and reads nothing. The others pass over the contact array
+ *   once, grid-wide. b2hip_fixture_set_sensors / _thicks then list the contacts whose candidacy for continuous collision
+ *   changes - four bytes come back: the length - sort the list, and one lane replays it (a world without continuous collision
+ *   lists nothing). b2hip_fixture_set_sensors reads the body-state table first if a batched write or a lazy world has left
+ *   it on the device, as the single call does.
+ * Out of scope: sharded worlds; calls inside a step or a listener callback; fixture creation and destruction; b2Body::SetType,
+ *   SetBullet and ResetMassData for many bodies; the drop-in C++ classes (b2Fixture's setters bind the single calls). */
+typedef struct b2hip_fixture_filter
+{
+	uint16_t category_bits, mask_bits;
+	int16_t  group_index;
+	uint16_t pad;        /* 0 */
+} b2hip_fixture_filter;
+typedef struct b2hip_fixture_material
+{
+	float density, friction, restitution;
+} b2hip_fixture_material;
+#define B2HIP_MATERIAL_DENSITY 1
+#define B2HIP_MATERIAL_FRICTION 2
+#define B2HIP_MATERIAL_RESTITUTION 4
+
+int b2hip_fixture_set_filters(b2hip_world* w, int n, const int32_t* fixtures, const b2hip_fixture_filter* filters);
+/* sensor / thick: one byte per entry, 0 = false, non-zero = true */
+int b2hip_fixture_set_sensors(b2hip_world* w, int n, const int32_t* fixtures, const uint8_t* sensor);
+int b2hip_fixture_set_thicks(b2hip_world* w, int n, const int32_t* fixtures, const uint8_t* thick);
+/* mask: a non-empty subset of B2HIP_MATERIAL_DENSITY | B2HIP_MATERIAL_FRICTION | B2HIP_MATERIAL_RESTITUTION */
+int b2hip_fixture_set_materials(b2hip_world* w, int n, const int32_t* fixtures, const b2hip_fixture_material* materials, int mask);
 
 #ifdef __cplusplus
 }
