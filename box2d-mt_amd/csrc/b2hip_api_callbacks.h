@@ -408,7 +408,7 @@ int b2hip_test_radix_sort(b2hip_world* w, int count, uint64_t* keys, int* payloa
 	if (!rc) rc = v0.ensure(room, s, false, false);
 	if (!rc) rc = v1.ensure(room, s, false, false);
 	if (!rc) rc = nDev.ensure(1, s, false, true);
-	auto done = [&](int code) { (void)hipStreamSynchronize(s); k0.release(); k1.release(); v0.release(); v1.release(); nDev.release(); return code; };
+	auto done = [&](int code) { (void)hipStreamSynchronize(s); return code; }; // (the arrays free themselves: not under a running stream)
 	if (rc) return done(rc);
 	hipError_t e = hipMemcpyAsync(nDev.p, &count, sizeof(int), hipMemcpyHostToDevice, s);
 	if (e == hipSuccess && count > 0) e = hipMemcpyAsync(k0.p, keys, (size_t)count * sizeof(uint64_t), hipMemcpyHostToDevice, s);
@@ -496,13 +496,27 @@ int b2hip_test_keyset_check(b2hip_world* w, long long out[6])
 	if (e == hipSuccess) e = hipMemcpyAsync(h, sums.p, sizeof(h), hipMemcpyDeviceToHost, w->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
 	else (void)hipStreamSynchronize(w->stream);
-	sums.release();
 	if (e != hipSuccess) return setError(B2HIP_ERR_HIP, hipGetErrorString(e));
 	out[1] = (long long)h[0];
 	out[2] = (long long)h[2] - (long long)h[1];
 	out[3] = (long long)h[2] + (long long)h[3] - (long long)c.ksFill;
 	out[4] = (long long)h[2];
 	out[5] = (long long)h[3];
+	return 0;
+}
+
+// Test hook: who owns what. out[0] the blocks the owner types (DevArray, PinnedBuf) hold in this process right now - what a
+// destroyed world leaves behind shows as a count that does not come back; out[1] the arrays of WORLD_ARRAYS_DW whose pointer
+// in the world's kernarg block is not the array's own (0 without a world).
+int b2hip_test_storage(b2hip_world* w, long long out[2])
+{
+	if (!out) return setError(B2HIP_ERR_INVALID, "null argument");
+	out[0] = g_liveBlocks.load();
+	out[1] = 0;
+	if (!w) return 0;
+#define X(T, name, count, keep, zeroNew) out[1] += w->dw.name != w->name.p;
+	WORLD_ARRAYS_DW(X)
+#undef X
 	return 0;
 }
 

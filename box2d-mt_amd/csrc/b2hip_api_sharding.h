@@ -173,10 +173,9 @@ static int spAllGather(b2hip_world* w, size_t words)
 	const size_t need = words * (size_t)(ranks + 1);
 	if (w->spHostWords < need)
 	{
-		if (w->spHost) (void)hipHostFree(w->spHost);
-		w->spHost = nullptr;
+		w->spHostWords = 0;
+		if (int rc = w->spHost.alloc(2 * need, hipHostMallocDefault)) return rc;
 		w->spHostWords = 2 * need;
-		HIP_TRY(hipHostMalloc((void**)&w->spHost, w->spHostWords * sizeof(int), hipHostMallocDefault));
 	}
 	HIP_TRY(hipMemcpyAsync(w->spHost, w->spSend.p, words * sizeof(int), hipMemcpyDeviceToHost, w->stream));
 	HIP_TRY(hipStreamSynchronize(w->stream));
@@ -215,13 +214,12 @@ static int spReadHeaders(b2hip_world* w, size_t strideWords, int (*hdr)[SP_HEADE
 	const int ranks = w->dw.shardCount;
 	if (!w->spHdrHost)
 	{
-		HIP_TRY(hipHostMalloc((void**)&w->spHdrHost, (2 + SHARD_MAX_RANKS * SP_HEADER_WORDS) * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-		HIP_TRY(hipHostGetDevicePointer((void**)&w->spHdrDev, w->spHdrHost, 0));
+		if (int rc = w->spHdrHost.alloc(2 + SHARD_MAX_RANKS * SP_HEADER_WORDS, hipHostMallocMapped | hipHostMallocCoherent)) return rc;
 		w->spHdrHost[0] = 0;
 	}
 	w->spHdrSeq = (w->spHdrSeq + 1) & 0x3fffffff;
 	if (w->spHdrSeq == 0) w->spHdrSeq = 1;
-	LAUNCH(w, k_sp_collect_headers, 1, 64, (const int*)w->spRecv.p, strideWords, ranks, extraDev, w->spHdrDev, w->spHdrSeq);
+	LAUNCH(w, k_sp_collect_headers, 1, 64, (const int*)w->spRecv.p, strideWords, ranks, extraDev, w->spHdrHost.dev, w->spHdrSeq);
 	if (int rc = pollPublished(w, (volatile const int*)&w->spHdrHost[0], w->spHdrSeq, "exchange headers of a spatially sharded world")) return rc;
 	memcpy(hdr, w->spHdrHost + 2, (size_t)ranks * SP_HEADER_WORDS * sizeof(int));
 	if (extra) *extra = w->spHdrHost[1];

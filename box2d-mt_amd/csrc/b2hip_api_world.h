@@ -67,36 +67,6 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 		delete w;
 		return setError(B2HIP_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
 	}
-	w->nextNode = 0;
-	w->leafCount = 0;
-	w->upBodies = w->upFixtures = w->upShapes = w->upJoints = 0;
-	w->stateCount = 0;
-	w->mirrorEpoch = 1;
-	w->stepEpoch = 1;
-	w->newFixture = false;
-	w->inv_dt0 = 0.0f;
-	w->stepActive = false;
-	w->callbackWindow = false;
-	w->h_state = nullptr;
-	w->h_stateCap = 0;
-	w->lastContacts = 0;
-	memset(&w->last, 0, sizeof(w->last));
-	memset(&w->dw, 0, sizeof(w->dw));
-	memset(w->profile, 0, sizeof(w->profile));
-	w->solverMs = 0.0f;
-	w->solverBytes = 0.0;
-	w->solverConstraints = w->solverBodies = 0;
-	w->kernelTiming = 0;
-	w->ktUnitsA = w->ktUnitsB = 0;
-	w->ktUsed = 0;
-	w->ktKind = 0;
-	w->ktMs = 0.0f;
-	w->ktLaunches = 0;
-	w->ktBytes = 0.0;
-	w->dw.cellSize = 1.0f;
-	w->dw.invCellSize = 1.0f;
-	w->colorSmallPending = false;
-	w->hubSteps = 0;
 	readSwitches(w);
 	{
 		// how many workgroups of the solvers whose workgroups wait for one another are resident together on this device
@@ -135,45 +105,21 @@ int b2hip_world_create(const b2hip_world_def* def, b2hip_world** out)
 				w->restHubMaxWG = std::min(f1, f2) * cus;
 		}
 	}
-	w->dfEpoch = 0;
-	for (int i = 0; i < 13; ++i) w->ev[i] = nullptr;
-	w->h_dstate = nullptr;
-	for (int i = 0; i < 13; ++i)
+	int rc = 0;
+	for (int i = 0; i < 13 && !rc; ++i)
+		if (hipEventCreate(&w->ev[i]) != hipSuccess) rc = setError(B2HIP_ERR_HIP, "hipEventCreate failed");
+	// (h_pub, h_pub2, h_solverWord: written by a kernel, polled by the host - mapped and coherent)
+	if (!rc) rc = w->h_dstate.alloc(1, hipHostMallocDefault);
+	if (!rc) rc = w->h_pub.alloc(1, hipHostMallocMapped | hipHostMallocCoherent);
+	if (!rc) rc = w->h_pub2.alloc(1, hipHostMallocMapped | hipHostMallocCoherent);
+	if (!rc) rc = w->h_solverWord.alloc(16, hipHostMallocMapped | hipHostMallocCoherent);
+	if (!rc)
 	{
-		if (hipEventCreate(&w->ev[i]) != hipSuccess)
-		{
-			b2hip_world_destroy(w);
-			return setError(B2HIP_ERR_HIP, "hipEventCreate failed");
-		}
+		memset(w->h_pub, 0, sizeof(DState));
+		memset(w->h_pub2, 0, sizeof(DState));
+		memset(w->h_solverWord, 0, 16 * sizeof(int));
+		rc = ensureCapacity(w, 0);
 	}
-	if (hipHostMalloc((void**)&w->h_dstate, sizeof(DState), hipHostMallocDefault) != hipSuccess)
-	{
-		b2hip_world_destroy(w);
-		return setError(B2HIP_ERR_HIP, "hipHostMalloc failed");
-	}
-	// (written by a kernel, polled by the host: mapped and coherent)
-	if (hipHostMalloc((void**)&w->h_pub, sizeof(DState), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-		hipHostGetDevicePointer((void**)&w->d_pub, w->h_pub, 0) != hipSuccess)
-	{
-		b2hip_world_destroy(w);
-		return setError(B2HIP_ERR_HIP, "hipHostMalloc (coherent) failed");
-	}
-	memset(w->h_pub, 0, sizeof(DState));
-	if (hipHostMalloc((void**)&w->h_pub2, sizeof(DState), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-		hipHostGetDevicePointer((void**)&w->d_pub2, w->h_pub2, 0) != hipSuccess)
-	{
-		b2hip_world_destroy(w);
-		return setError(B2HIP_ERR_HIP, "hipHostMalloc (coherent) failed");
-	}
-	memset(w->h_pub2, 0, sizeof(DState));
-	if (hipHostMalloc((void**)&w->h_solverWord, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-		hipHostGetDevicePointer((void**)&w->d_solverWord, w->h_solverWord, 0) != hipSuccess)
-	{
-		b2hip_world_destroy(w);
-		return setError(B2HIP_ERR_HIP, "hipHostMalloc (coherent) failed");
-	}
-	memset(w->h_solverWord, 0, 64);
-	int rc = ensureCapacity(w, 0);
 	if (rc == 0 && hipStreamSynchronize(w->stream) != hipSuccess) rc = setError(B2HIP_ERR_HIP, "stream sync failed");
 	if (rc)
 	{
@@ -200,65 +146,9 @@ void b2hip_world_destroy(b2hip_world* w)
 	}
 	if (w->shardComm != nullptr && g_rcclDestroy != nullptr) g_rcclDestroy(w->shardComm);
 	w->shardComm = nullptr;
-	w->shardSend.release(); w->shardRecv.release();
-	w->b_owner.release(); w->spNewOwner.release(); w->spAwake.release(); w->spStraddle.release(); w->spCount.release(); w->spTarget.release();
-	w->spSend.release(); w->spRecv.release(); w->spTailKey.release(); w->spVirt.release();
-	if (w->spHost) (void)hipHostFree(w->spHost);
-	w->spHost = nullptr;
-	if (w->spOwnHost) (void)hipHostFree(w->spOwnHost);
-	w->spOwnHost = nullptr;
-	if (w->spHdrHost) (void)hipHostFree(w->spHdrHost);
-	w->spHdrHost = nullptr;
 	for (size_t k = 0; k < w->spTape.size(); ++k) (void)hipFree(w->spTape[k].first);
 	w->spTape.clear();
-	w->d_state.release();
-	w->b_pos.release(); w->b_pos0.release(); w->b_vel.release(); w->b_xf.release(); w->b_mass.release(); w->b_damp.release();
-	w->b_force.release(); w->b_flags.release(); w->b_wake.release(); w->b_rowDirty.release();
-	w->p_fat.release(); w->p_body.release(); w->p_shape.release(); w->p_key.release(); w->p_filter0.release(); w->p_filter1.release();
-	w->p_mat.release(); w->d_shapes.release();
-	for (int k = 0; k < 2; ++k)
-	{
-		w->c_ids[k].release(); w->c_key[k].release(); w->c_flags[k].release(); w->c_mat[k].release(); w->c_man0[k].release();
-		w->c_man1[k].release(); w->c_imp[k].release(); w->c_man3[k].release(); w->c_color[k].release();
-	}
-	w->ht_keys.release(); w->d_joints.release(); w->d_gears.release(); w->li_ref.release();
-	w->jadjStart.release(); w->jadj.release(); w->rootJointStart.release(); w->rootJointCursor.release();
-	w->lj_list.release(); w->rootJointOkay.release();
-	w->parent.release(); w->rootSeed.release(); w->rootBodies.release(); w->rootContacts.release(); w->rootJoints.release();
-	w->rootIsland.release(); w->deg.release(); w->adjStart.release(); w->adjCursor.release(); w->adj.release(); w->adjSlot.release();
-	w->rootScanIn.release(); w->rootScanOut.release();
-	w->si_root.release(); w->si_bodyStart.release(); w->si_contactStart.release(); w->si_wStart.release(); w->si_maxLevel.release();
-	w->si_bodies.release(); w->si_contacts.release(); w->si_level.release(); w->si_stack.release(); w->si_lastLevel.release();
-	w->b_slot.release(); w->b_island.release(); w->chunkFirst.release();
-	w->li_bodies.release(); w->li_contacts.release(); w->li_roots.release(); w->li_color.release(); w->colorCount.release();
-	w->colorStart.release(); w->colorCursor.release(); w->li_sorted.release(); w->bodyClaim.release(); w->rootPen.release();
-	w->bodyActive.release(); w->bodyRest.release(); w->b_posv.release(); w->evKey.release(); w->evInfo.release(); w->uncolList.release(); w->compactList.release(); w->gridBar.release(); w->hubRowOf.release(); w->hubList.release(); w->hubDelta.release(); w->hubMeta.release(); w->hubFirst.release(); w->solveSnapBody.release(); w->solveSnapImp.release(); w->solveSnapCFlags.release(); w->solveSnapJoints.release(); w->solveSnapGears.release();
-	w->b_proxyHead.release(); w->p_next.release(); w->toiList.release(); w->toiPos2c.release(); w->toiDestroyList.release(); w->toiNewList.release(); w->collideCounts.release(); w->collideGroups.release();
-	w->b_toiGroup.release(); w->toiGroups.release(); w->toiGroupCount.release(); w->toiGroupList.release(); w->toiMoved.release(); w->toiNew.release(); w->toiParent.release(); w->toiDomOf.release(); w->toiDomRoot.release(); w->toiDomCount.release(); w->toiDomBase.release(); w->toiDomFill.release(); w->toiDomFailed.release(); w->toiDomEvents.release(); w->toiDomList.release(); w->toiHull.release(); w->snapBody.release(); w->snapFat.release();
-	w->c_mgr[0].release(); w->c_mgr[1].release(); w->dbgPreVel.release(); w->dbgVel.release(); w->dbgLi.release();
-	w->rootSleepMin.release(); w->bodyColorMask.release(); w->rootDone.release(); w->lc.release(); w->warmDelta.release();
-	w->moveBuf.release(); w->gridCount.release(); w->gridStart.release(); w->gridCursor.release(); w->gridItems.release(); w->gridFat.release(); w->arriveTree.release();
-	w->largeProxies.release(); w->largeMoves.release(); w->pairKey.release(); w->pairKey2.release(); w->pairProxy.release(); w->pairProxy2.release();
-	w->filterPairs.release();
-	w->d_editOps.release();
-	w->b_order.release(); w->orderBody.release(); w->bigRoots.release();
-	w->pre_o0.release(); w->pre_o1.release(); w->pre_oimp.release(); w->pre_o3.release(); w->preRecs.release();
-	w->postRecs.release(); w->filterList.release(); w->hostList.release(); w->toiLog.release(); w->toiVerdict.release();
-	w->b_blk1.release(); w->b_adopt.release(); w->b_adoptStage.release(); w->blkRows.release(); w->blkRowStart.release(); w->blkCursor.release(); w->blkBodyCount.release(); w->blkBodyCursor.release();
-	w->blkBodyStart.release(); w->blkBodies.release(); w->rowColor.release(); w->b_cutv.release();
-	w->pairFirst.release(); w->pairRank.release(); w->scanTmp.release(); w->radixHist.release(); w->radixHistScan.release();
-	w->keepFlag.release(); w->keepScan.release(); w->scanTmp4.release(); w->scanFlags.release(); w->radixCounts.release(); w->radixGroups.release(); w->radixGlobalHist.release(); w->stateOut.release(); w->consts.release();
-	w->qIn.release(); w->qCounts.release(); w->qOffsets.release(); w->qItems.release(); w->qFlags.release(); w->qScanWork.release();
-	w->qScanWords.release(); w->qWords.release(); w->qHits.release(); w->qDistances.release(); w->qPoses.release(); w->qShapes.release();
-	w->qKeys.release(); w->qKeysWork.release(); w->qAny.release();
-	w->bcSlot.release(); w->bcIds.release(); w->bcCounts.release(); w->bcRecords.release(); w->bcTotals.release();
-	w->bwIn.release(); w->bwRows.release(); w->jbOut.release(); w->lcNamed.release(); w->lcWords.release(); w->fxNamed.release();
 	if (w->qPinned) (void)hipHostFree(w->qPinned);
-	if (w->h_state) (void)hipHostFree(w->h_state);
-	if (w->h_dstate) (void)hipHostFree(w->h_dstate);
-	if (w->h_pub) (void)hipHostFree(w->h_pub);
-	if (w->h_pub2) (void)hipHostFree(w->h_pub2);
-	if (w->h_solverWord) (void)hipHostFree(w->h_solverWord);
 	for (int i = 0; i < 13; ++i)
 		if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
 	for (size_t i = 0; i < w->ktEvents.size(); ++i) (void)hipEventDestroy(w->ktEvents[i]);
@@ -266,7 +156,7 @@ void b2hip_world_destroy(b2hip_world* w)
 	if (w->stream2) (void)hipStreamDestroy(w->stream2);
 	if (w->evFork) (void)hipEventDestroy(w->evFork);
 	if (w->evJoin) (void)hipEventDestroy(w->evJoin);
-	delete w;
+	delete w; // (frees the device arrays and the pinned buffers, with the world's device still current)
 }
 
 int b2hip_set_gravity(b2hip_world* w, float gx, float gy)

@@ -438,7 +438,7 @@ static int buildIslands(b2hip_world* w, const SolveStep& s)
 	deviceExclusiveScan<int>(w->stream, d.deg, d.adjStart, d.scanTmp, w->scanCtx, w->consts.p, d.nBodies);
 	if (d.nJoints > 0) deviceExclusiveScan<int>(w->stream, d.rootJoints, d.rootJointStart, d.scanTmp, w->scanCtx, w->consts.p, d.nBodies);
 	LAUNCH(w, k_island_assign, gridFor(d.nBodies), 256, d);
-	LAUNCH(w, k_island_edges, gSolid, 256, d, pubBy == 2 ? w->d_pub : (DState*)nullptr, solidRounds);
+	LAUNCH(w, k_island_edges, gSolid, 256, d, pubBy == 2 ? w->h_pub.dev : (DState*)nullptr, solidRounds);
 	// (a growing pile: hand home blocks on to newcomers up to four contacts away instead of partitioning again)
 	if (adopt)
 		for (int stage = 0; stage < 3; ++stage) LAUNCH(w, k_block_adopt, gridFor(d.capContacts), 256, d, stage);
@@ -448,9 +448,9 @@ static int buildIslands(b2hip_world* w, const SolveStep& s)
 	{
 		LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
 		LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
-		LAUNCH(w, k_block_census, 1, 1024, d, pubBy == 1 ? w->d_pub : (DState*)nullptr);
+		LAUNCH(w, k_block_census, 1, 1024, d, pubBy == 1 ? w->h_pub.dev : (DState*)nullptr);
 	}
-	if (pubBy == 3) LAUNCH(w, k_publish_census, 1, 256, d, w->d_pub);
+	if (pubBy == 3) LAUNCH(w, k_publish_census, 1, 256, d, w->h_pub.dev);
 	return 0;
 }
 
@@ -469,7 +469,7 @@ static int awaitIslandCensus(b2hip_world* w, SolveStep& s)
 		// the host's own hysteresis in largeIslandPolicy - the queued launch runs too and PUBLISHES what it leaves: the
 		// launch-per-colour path polls that instead of a copy + synchronise)
 		const int aheadMinRows = s.exactLarge ? 0 : (w->noBlocks ? 1 : (w->blocksTooBig ? 650 * std::max(w->blocksMaxWG, w->sweepMaxWG[2]) : 0));
-		if (s.largeHint && !s.exactLarge) { LAUNCH(w, k_color_small, 1, 1024, d, 1, aheadMinRows, w->d_pub2, (w->pubSeq2 + 1) & 0x3fffffff); s.colorSmallQueued = true; }
+		if (s.largeHint && !s.exactLarge) { LAUNCH(w, k_color_small, 1, 1024, d, 1, aheadMinRows, w->h_pub2.dev, (w->pubSeq2 + 1) & 0x3fffffff); s.colorSmallQueued = true; }
 		rc = awaitCensus(w);
 		if (rc == 0)
 		{
@@ -768,7 +768,7 @@ static int colorLargeIslands(b2hip_world* w, SolveStep& s)
 		if (!s.colorSmallQueued)
 		{
 			if (pubColors) w->pubSeq2 = (w->pubSeq2 + 1) & 0x3fffffff;
-			LAUNCH(w, k_color_small, 1, 1024, d, 0, 0, pubColors ? w->d_pub2 : (DState*)nullptr, w->pubSeq2); // (else: it went out behind the census)
+			LAUNCH(w, k_color_small, 1, 1024, d, 0, 0, pubColors ? w->h_pub2.dev : (DState*)nullptr, w->pubSeq2); // (else: it went out behind the census)
 		}
 		if (s.useBlocks)
 		{
@@ -1248,7 +1248,7 @@ static int recoverLarge(b2hip_world* w, SolveStep& s)
 {
 	DW& d = w->dw;
 	w->solverSeq = (w->solverSeq + 1) & 0x7fff;
-	LAUNCH(w, k_solver_status, 1, 64, d, w->d_solverWord, w->solverSeq);
+	LAUNCH(w, k_solver_status, 1, 64, d, w->h_solverWord.dev, w->solverSeq);
 	if (int rc = pollPublished(w, (volatile const int*)&w->h_solverWord[1], w->solverSeq, "solver status")) return rc;
 	const int flags = w->h_solverWord[0];
 	// (k_solve_blocks read the colours on the device: were they complete?)
@@ -1507,7 +1507,7 @@ static int downloadState(b2hip_world* w, int clearForces, bool skipRowsIfRedo)
 	if (w->traceLaunches) fprintf(stderr, "[b2hip] host: read-back: rows went early %d, row mode %d, lazy %d, clearing %d (clear %d), marks %d\n", (int)w->rowsWentEarly, rowMode, (int)lazy, (int)clearing, clear, w->rowMarks);
 	const int marks = (w->rowsWentEarly && rowMode == 2 && !lazy && !w->spatial && !clearing && !d.toiContinue && d.toiEventCap == 0) ? w->rowMarks : 0;
 	w->rowsWentEarly = false;
-	LAUNCH(w, k_end_step, gridFor(d.nBodies), 256, d, clear, (const int*)w->gridBar.p, w->d_hstate, w->stateSeq,
+	LAUNCH(w, k_end_step, gridFor(d.nBodies), 256, d, clear, (const int*)w->gridBar.p, w->h_state.dev, w->stateSeq,
 		lazy ? END_STEP_LAZY : skipRowsIfRedo ? END_STEP_SKIP_IF_REDO : END_STEP_FULL, w->stateOut.p, rowMode, marks);
 	if (w->traceLaunches) { fprintf(stderr, "[b2hip] host: awaiting the read-back %d\n", w->stateSeq); fflush(stderr); }
 	const int rc = awaitState(w, nb);
@@ -1531,7 +1531,7 @@ static int fetchRows(b2hip_world* w)
 	if (w->stateSeq == 0) w->stateSeq = 1;
 	((DState*)(w->h_state + B2D_STATE_TAIL(nb)))->pubSeq = 0;
 	const int rowMode = shadowValid(w) ? 2 : 1;
-	LAUNCH(w, k_end_step, gridFor(d.nBodies), 256, d, 0, (const int*)nullptr, w->d_hstate, w->stateSeq, END_STEP_ROWS, w->stateOut.p, rowMode, 0);
+	LAUNCH(w, k_end_step, gridFor(d.nBodies), 256, d, 0, (const int*)nullptr, w->h_state.dev, w->stateSeq, END_STEP_ROWS, w->stateOut.p, rowMode, 0);
 	const int rc = pollPublished(w, (volatile const int*)&((const DState*)(w->h_state + B2D_STATE_TAIL(nb)))->pubSeq, w->stateSeq, "lazy state read-back");
 	if (rc == 0 && rowMode == 1) shadowWritten(w);
 	return rc;

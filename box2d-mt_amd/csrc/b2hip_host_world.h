@@ -21,39 +21,87 @@ static int setError(int code, const std::string& msg)
 		}                                                                                               \
 	} while (0)
 
-// Device array that keeps its content when it grows.
 // (set when librccl is opened, b2hip_shard_connect: releases a world's communicator)
 static void (*g_rcclDestroy)(void* comm) = nullptr;
 
+// Blocks that the two owner types below hold in this process right now (b2hip_test_storage).
+static std::atomic<long long> g_liveBlocks{0};
+
+// Device array that keeps its content when it grows and frees its block when it goes. Whoever lets one go drains the
+// streams that use it first and has its device current (b2hip_world_destroy).
 template <typename T>
 struct DevArray
 {
 	T* p = nullptr;
 	size_t cap = 0;
+	DevArray() = default;
+	DevArray(const DevArray&) = delete;
+	DevArray& operator=(const DevArray&) = delete;
+	~DevArray() { drop(p); }
+	// the capacity ensure(n) leaves: 64 at least, doubled until n fits
+	size_t capFor(size_t n) const
+	{
+		if (n <= cap) return cap;
+		size_t ncap = cap ? cap : 64;
+		while (ncap < n) ncap *= 2;
+		return ncap;
+	}
 	int ensure(size_t n, hipStream_t stream, bool keep = true, bool zeroNew = true)
 	{
 		if (n <= cap) return 0;
-		size_t ncap = cap ? cap : 64;
-		while (ncap < n) ncap *= 2;
+		const size_t ncap = capFor(n);
 		T* np = nullptr;
 		HIP_TRY(hipMalloc((void**)&np, ncap * sizeof(T)));
+		g_liveBlocks += 1;
+		struct Fresh { T* q; ~Fresh() { drop(q); } } fresh = { np }; // (freed again on every way out but the last)
 		if (zeroNew) HIP_TRY(hipMemsetAsync(np, 0, ncap * sizeof(T), stream));
 		if (keep && p && cap) HIP_TRY(hipMemcpyAsync(np, p, cap * sizeof(T), hipMemcpyDeviceToDevice, stream));
 		if (p)
 		{
 			HIP_TRY(hipStreamSynchronize(stream));
 			HIP_TRY(hipFree(p));
+			g_liveBlocks -= 1;
 		}
+		fresh.q = nullptr;
 		p = np;
 		cap = ncap;
 		return 0;
 	}
-	void release()
+private:
+	static void drop(T* q)
 	{
-		if (p) (void)hipFree(p);
-		p = nullptr;
-		cap = 0;
+		if (q) { (void)hipFree(q); g_liveBlocks -= 1; }
 	}
+};
+
+// Pinned host memory, typed, freed when its owner goes; dev is its device address where it was allocated mapped. Reads as the
+// host pointer it holds.
+template <typename T>
+struct PinnedBuf
+{
+	T* p = nullptr;
+	T* dev = nullptr;
+	PinnedBuf() = default;
+	PinnedBuf(const PinnedBuf&) = delete;
+	PinnedBuf& operator=(const PinnedBuf&) = delete;
+	~PinnedBuf() { free(); }
+	// count elements, not initialised; what it held before is freed first
+	int alloc(size_t count, unsigned flags)
+	{
+		free();
+		HIP_TRY(hipHostMalloc((void**)&p, count * sizeof(T), flags));
+		g_liveBlocks += 1;
+		if (flags & hipHostMallocMapped) HIP_TRY(hipHostGetDevicePointer((void**)&dev, p, 0));
+		return 0;
+	}
+	void free()
+	{
+		if (p) { (void)hipHostFree(p); g_liveBlocks -= 1; }
+		p = dev = nullptr;
+	}
+	void swap(PinnedBuf& o) { std::swap(p, o.p); std::swap(dev, o.dev); }
+	T* operator->() const { return p; }
+	operator T*() const { return p; }
 };
 
 struct HostBody
@@ -158,12 +206,206 @@ struct ToiStats // since the world was created; n[] in the order b2hip_debug_rea
 	long long chainContacts = 0; // contacts created by the close-out of the parallel TOI chains
 };
 
+// ---- the device arrays that ensureCapacity sizes: X(type, name, count, keep, zeroNew), one line each ------------------------
+// Three expansions - the members of b2hip_world, ensureCapacity's loop, and for the first list `d.name = w->name.p` - and
+// b2hip_test_storage's check of the last. The counts are read inside ensureCapacity: z is its WorldSizes, w the world. An
+// array whose name is not here is sized where it is used, or by hand at the top of ensureCapacity.
+// WORLD_ARRAYS_DW: DW holds the array's pointer under the same name.
+#define WORLD_ARRAYS_DW(X) \
+	X(float4, b_pos, z.nb, true, true) \
+	X(float4, b_pos0, z.nb, true, true) \
+	X(float4, b_vel, z.nb, true, true) \
+	X(float4, b_xf, z.nb, true, true) \
+	X(float4, b_mass, z.nb, true, true) \
+	X(float4, b_damp, z.nb, true, true) \
+	X(float4, b_force, z.nb, true, true) \
+	X(uint32_t, b_flags, z.nb, true, true) \
+	X(int, b_wake, z.nb, true, true) \
+	X(int, b_rowDirty, z.nb, true, true) \
+	X(int, b_order, z.nb, true, true) \
+	X(int, orderBody, z.nb, true, true) \
+	X(int, bigRoots, SHARD_BIG_MAX, true, true) /* sharded worlds: roots of this step's big islands */ \
+	X(float4, p_fat, z.np, true, true) \
+	X(int, p_body, z.np, true, true) \
+	X(int, p_shape, z.np, true, true) \
+	X(int, p_key, z.np, true, true) \
+	X(uint32_t, p_filter0, z.np, true, true) \
+	X(int, p_filter1, z.np, true, true) \
+	X(float2, p_mat, z.np, true, true) \
+	X(int, b_proxyHead, z.nb, true, true) \
+	X(int, p_next, z.np, true, true) \
+	/* k_solver_snapshot (b2d_kernels_sweep_end.h): what a recovered solve goes back to; B2HIP_NO_RECOVER=1: one element each */ \
+	X(RevoluteJoint, solveSnapJoints, w->recoverOn ? z.nj : 1, true, true) \
+	X(GearRec, solveSnapGears, w->recoverOn ? z.ng : 1, true, true) \
+	X(int, jadjStart, z.nb + 2, true, true) \
+	X(int, jadj, 2 * w->joints.size() + 2, true, true) \
+	X(int, rootJointStart, z.nb + 2, true, true) \
+	X(int, rootJointCursor, z.nb, true, true) \
+	X(int, lj_list, w->joints.size() + 2, true, true) \
+	X(int, rootJointOkay, z.nb, true, true) \
+	X(int, parent, z.nb, true, true) \
+	X(int, rootSeed, z.nb, true, true) \
+	X(int, rootBodies, z.nb, true, true) \
+	X(int, rootContacts, z.nb, true, true) \
+	X(int, rootJoints, z.nb, true, true) \
+	X(int, rootIsland, z.nb, true, true) \
+	X(int, deg, z.nb + 1, true, true) \
+	X(int, adjStart, z.nb + 2, true, true) \
+	X(int, adjCursor, z.nb, true, true) \
+	X(int, adj, 2 * z.cc, true, true) \
+	X(int2, adjSlot, z.cc, true, true) \
+	X(int4, rootScanIn, z.nb + 1, true, true) \
+	X(int4, rootScanOut, z.nb + 2, true, true) \
+	X(int, si_root, z.nb + 1, true, true) \
+	X(int, si_bodyStart, z.nb + 2, true, true) \
+	X(int, si_contactStart, z.nb + 2, true, true) \
+	X(int, si_wStart, z.nb + 2, true, true) \
+	X(int, si_maxLevel, z.nb + 1, true, true) \
+	X(int, si_bodies, z.nb, true, true) \
+	X(int, si_contacts, z.cc, true, true) \
+	X(int, si_level, z.cc, true, true) \
+	X(int, si_stack, z.nb, true, true) \
+	X(int, si_lastLevel, z.nb, true, true) \
+	X(int, b_slot, z.nb, true, true) \
+	X(int, b_island, z.nb, true, true) \
+	X(int, chunkFirst, (z.nb + z.cc) / (TINY_CHUNK_LANES / 2) + 4, true, true) \
+	X(int, li_bodies, z.nb, true, true) \
+	X(int, li_contacts, z.cc, true, true) \
+	X(int, li_roots, z.nb, true, true) \
+	X(int, li_color, z.cc, true, true) \
+	/* (colorSlot: the first 65 colour counters on a line each) */ \
+	X(int, colorCount, z.cc + 2 + COLOR_SLOT_PADDED * COLOR_SLOT_STRIDE, true, true) \
+	X(int, colorStart, z.cc + 2, true, true) \
+	X(int, colorCursor, z.cc + 2 + COLOR_SLOT_PADDED * COLOR_SLOT_STRIDE, true, true) \
+	X(int, li_sorted, z.cc, true, true) \
+	X(int4, li_ref, z.cc, true, true) \
+	X(uint32_t, bodyClaim, z.nb, true, true) \
+	X(uint64_t, bodyColorMask, z.nb, true, true) \
+	X(uint64_t, bodyActive, z.nb, true, true) \
+	X(uint64_t, bodyRest, z.nb, true, true) \
+	X(float4, b_posv, z.nb, true, true) \
+	X(unsigned long long, evKey, z.cc, true, true) \
+	X(int4, evInfo, z.cc, true, true) \
+	X(int, uncolList, COLOR_SMALL_MAX, true, true) \
+	X(int, compactList, COLOR_SMALL_MAX, true, true) \
+	X(int, hubRowOf, z.cc, true, true) \
+	X(int, hubList, z.cc, true, true) \
+	X(float4, hubDelta, z.cc, true, true) \
+	X(unsigned long long, hubMeta, 8, true, true) \
+	X(unsigned long long, hubFirst, z.nb, true, true) \
+	X(float4, solveSnapBody, w->recoverOn ? 6 * z.nb : 1, true, true) \
+	X(float4, solveSnapImp, w->recoverOn ? z.cc : 1, true, true) \
+	X(uint32_t, solveSnapCFlags, w->recoverOn ? z.cc : 1, true, true) \
+	X(uint32_t, rootPen, ROOT_PEN_SLOTS * z.nb, true, true) \
+	X(int, rootDone, z.nb, true, true) \
+	X(uint32_t, rootSleepMin, z.nb, true, true) \
+	X(float, lc, (size_t)LC_WORDS * z.cc, false, false) \
+	X(float4, warmDelta, 4 * z.cc, false, false) /* per-step scratch: k_large_init -> k_large_warm */ \
+	X(int, moveBuf, 2 * z.np + 64, true, true) \
+	X(int, gridCount, z.gridSize, true, true) \
+	X(int, gridStart, z.gridSize + 2, true, true) \
+	X(int, gridCursor, z.gridSize, true, true) \
+	X(int, gridItems, z.np, true, true) \
+	X(float4, gridFat, z.np, true, true) \
+	X(unsigned long long, arriveTree, (size_t)ARRIVE_SITES * TREE_WORDS, true, true) \
+	X(int, largeProxies, z.np, true, true) \
+	X(int, largeMoves, 2 * z.np + 64, true, true) \
+	X(uint64_t, pairKey, z.capPairs, true, true) \
+	X(uint64_t, pairKey2, z.capPairs, true, true) \
+	X(int2, pairProxy, z.capPairs, true, true) \
+	X(int2, pairProxy2, z.capPairs, true, true) \
+	X(int, pairFirst, z.capPairs + 1, true, true) \
+	X(int, pairRank, z.capPairs + 2, true, true) \
+	X(int, radixHist, RADIX_DIGITS * z.radixTiles + 2, true, true) \
+	X(int, scanTmp, 3 * (std::max(z.maxScanN, RADIX_DIGITS * z.radixTiles) / SCAN_TILE + 8), true, true) \
+	X(int, keepFlag, z.cc + 1, true, true) \
+	X(int, keepScan, z.cc + 2, true, true) \
+	X(int, toiList, z.cc, true, true) \
+	X(int, toiPos2c, z.cc, true, true) \
+	X(int, toiDestroyList, z.cc, true, true) \
+	X(int, toiNewList, TOI_NEW_LIST_MAX, true, true) \
+	X(int, b_toiGroup, z.nb, true, true) \
+	X(int, toiGroups, z.nb, true, true) \
+	X(int, toiGroupCount, std::min<size_t>(z.nb, TOI_GROUPS_MAX), true, true) \
+	X(int, toiGroupList, std::min<size_t>(z.nb, TOI_GROUPS_MAX) * CHAIN_ADJ_MAX, true, true) \
+	X(int, toiMoved, TOI_MOVED_ALL_MAX, true, true) \
+	X(int, toiNew, 8 * TOI_NEWPAIR_MAX, true, true) \
+	X(int, toiParent, z.nb, true, true) \
+	X(int, toiDomOf, z.nb, true, true) \
+	X(int, toiDomRoot, TOI_DOMAINS_MAX, true, true) \
+	X(int, toiDomCount, TOI_DOMAINS_MAX, true, true) \
+	X(int, toiDomBase, TOI_DOMAINS_MAX, true, true) \
+	X(int, toiDomFill, TOI_DOMAINS_MAX, true, true) \
+	X(int, toiDomFailed, TOI_DOMAINS_MAX, true, true) \
+	X(int, toiDomEvents, TOI_DOMAINS_MAX, true, true) \
+	X(int, toiDomList, z.cc, true, true) \
+	X(float4, toiHull, z.np, true, true) \
+	X(float4, snapBody, 5 * z.nb, true, true) \
+	X(float4, snapFat, z.np, true, true) \
+	/* listener bridge (nPre, nPost, nFil: contact-sized while the callback is installed) */ \
+	X(float4, pre_o0, z.nPre, true, true) \
+	X(float4, pre_o1, z.nPre, true, true) \
+	X(float4, pre_oimp, z.nPre, true, true) \
+	X(int4, pre_o3, z.nPre, true, true) \
+	X(PreSolveRec, preRecs, z.nPre, true, true) \
+	X(PostSolveRec, postRecs, z.nPost, true, true) \
+	X(int, filterList, z.nFil, true, true) \
+	/* block partition of the large islands (b2d_kernels_solve_blocks.h) */ \
+	X(int, b_blk1, z.nb, true, true) \
+	X(int, b_adopt, z.nb, true, true) \
+	X(int, b_adoptStage, 3 * z.nb, true, true) \
+	X(int, blkRows, (size_t)(MAX_BLOCKS + 2) * BLK_SLOT, true, true) \
+	X(int, blkRowStart, MAX_BLOCKS + 2, true, true) \
+	X(int, blkCursor, (size_t)(MAX_BLOCKS + 2) * BLK_SLOT, true, true) \
+	X(int, blkBodyCount, (size_t)(MAX_BLOCKS + 2) * BLK_SLOT, true, true) \
+	X(int, blkBodyCursor, (size_t)(MAX_BLOCKS + 2) * BLK_SLOT, true, true) \
+	X(int, blkBodyStart, MAX_BLOCKS + 2, true, true) \
+	X(int, blkBodies, z.nb, true, true) \
+	X(int, rowColor, z.cc, true, true) \
+	X(float4, b_cutv, z.nb, true, true) \
+	/* spatial ownership (b2d_kernels_spatial.h; b2hip_shard_spatial): one element each in every other world */ \
+	X(uint8_t, b_owner, w->spatial ? z.nb : 1, true, true) \
+	X(uint8_t, spNewOwner, w->spatial ? z.nb : 1, true, true) \
+	X(uint8_t, spAwake, w->spatial ? z.nb : 1, true, true) \
+	X(int, spStraddle, w->spatial ? std::max<size_t>(w->spStraddle.cap, 4096) : 1, true, true) \
+	X(int, spCount, w->spatial ? (size_t)SP_RESOLVE_MAX * SHARD_MAX_RANKS : 1, true, true) \
+	X(int, spTarget, w->spatial ? SP_RESOLVE_MAX : 1, true, true) \
+	X(int4, spTailKey, w->spatial ? z.capContacts : 1, true, true) \
+	/* (+ the counters, behind the rows: one copy to the host per step) */ \
+	X(float, stateOut, 12 * z.nb + sizeof(DState) / sizeof(float) + 4, true, true)
+
+// WORLD_ARRAYS_HOST: DW does not hold it - the host alone hands it to the kernels that use it - or holds its pointer only
+// under a condition, written behind the binds (toiLog, toiVerdict).
+#define WORLD_ARRAYS_HOST(X) \
+	X(int, radixHistScan, RADIX_DIGITS * z.radixTiles + 4, true, true) \
+	X(int4, scanTmp4, 3 * (z.maxScanN / SCAN_TILE + 8), true, true) \
+	/* status words of the single-pass scans (b2d_scan.h); a grown array keeps its words: the epoch goes on (scanCtx) */ \
+	X(int, scanFlags, std::max(z.maxScanN, RADIX_DIGITS * z.radixTiles) / SCAN_TILE + 8, true, true) \
+	/* status words of the one-launch radix passes (b2d_scan.h) for the pair buffers' tiles up to RADIX_ONEPASS_MAX_TILES (a sort */ \
+	/* over more takes the three-launch form), and the sorts' two global digit histograms. Here and for k_collide's words below */ \
+	/* a grown array starts from zeroed words under the running tag, which no word carries yet. */ \
+	X(unsigned, radixCounts, z.onepassTiles * RADIX_DIGITS, false, true) \
+	X(unsigned, radixGroups, z.onepassTiles ? (z.onepassTiles / RADIX_GROUP + 1) * RADIX_DIGITS : 0, false, true) \
+	X(int, radixGlobalHist, z.onepassTiles ? 2 * RADIX_MAX_PASSES * RADIX_DIGITS : 0, true, true) \
+	/* status words of k_collide<0, false, true>, a chunk's count / a group's sum each, for every chunk of the contact array */ \
+	X(unsigned, collideCounts, z.collideChunks, false, true) \
+	X(unsigned, collideGroups, z.collideChunks ? z.collideChunks / COLLIDE_GROUP + 2 : 0, false, true) \
+	X(ToiLogRec, toiLog, listenerOn(w) && w->def.continuous ? z.cc : 1, true, true) \
+	/* PreSolve answers for the TOI phase's log slots (DW::toiVerdict) */ \
+	X(int4, toiVerdict, hasPreSolve(w) && w->def.continuous ? z.cc : 1, true, true) \
+	/* indices uploaded by the host: contacts to disable / reject, pairs to drop (PreSolve material edits: 4 words each) */ \
+	X(int, hostList, std::max<size_t>(std::max(4 * z.nPre, z.nFil), hasFilter(w) ? z.capPairs : 1), true, true) \
+	/* body pairs a TOI event would have joined over an ownership boundary (k_sp_tail_pairs) */ \
+	X(int2, spVirt, w->spatial ? SP_TAIL_MAX + 1 : 1, true, true) \
+	X(int, consts, 16, true, true) /* [0] nBodies, [1] gridSize, [2] radix hist count, [3] sorted-pair count */ \
+	X(int, gridBar, 32, true, true) /* grid barrier state of the persistent solver */
+
 struct b2hip_world
 {
-	b2hip_world_def def;
-	int device;
-	hipStream_t stream;
-	bool debugSync;
+	b2hip_world_def def = {};
+	int device = -1;
+	hipStream_t stream = nullptr;
+	bool debugSync = false;
 
 	std::vector<HostBody> bodies;
 	std::vector<HostFixture> fixtures;
@@ -172,87 +414,53 @@ struct b2hip_world
 	std::vector<RevoluteJoint> joints;
 
 	// proxy id allocator (b2DynamicTree::AllocateNode / FreeNode, b2DynamicTree.cpp:53-99)
-	int nextNode;
-	int leafCount;
+	int nextNode = 0;
+	int leafCount = 0;
 	std::vector<FreeUnit> freeUnits;
 
 	// what has been uploaded so far
-	size_t upBodies, upFixtures, upShapes, upJoints;
+	size_t upBodies = 0, upFixtures = 0, upShapes = 0, upJoints = 0;
 	std::vector<int> pendingMoves;
 	std::vector<int> dirtyList;   // bodies whose host mirror is newer than the device rows
 	std::mutex dirtyMutex;        // the per-body setters may run on several user threads, one body each (ManyBodies.h:39-64)
-	size_t stateCount;            // bodies covered by the last read-back in h_state
-	uint32_t mirrorEpoch;         // bumped by every read-back into h_state (HostBody::pullEpoch)
-	uint32_t stepEpoch;           // bumped by every step (HostBody::forceEpoch)
-	bool newFixture;
-	float inv_dt0;
-	bool stepActive;
-	bool callbackWindow;          // inside the step, while the PreSolve callbacks run: mutators are accepted (and applied right after)
+	size_t stateCount = 0;        // bodies covered by the last read-back in h_state
+	uint32_t mirrorEpoch = 1;     // bumped by every read-back into h_state (HostBody::pullEpoch)
+	uint32_t stepEpoch = 1;       // bumped by every step (HostBody::forceEpoch)
+	bool newFixture = false;
+	float inv_dt0 = 0.0f;
+	bool stepActive = false;
+	bool callbackWindow = false;  // inside the step, while the PreSolve callbacks run: mutators are accepted (and applied right after)
 	bool failed = false;          // a step failed half-way: the device state is inconsistent, every later call says so
 	std::string failedWhy;
-	StepParams sp;
+	StepParams sp = {};
 
-	// device
-	DW dw;
+	// device: the kernarg block, the arrays of the two tables, and the ones ensureCapacity sizes by hand - the state block, the
+	// tables whose names differ from DW's (shapes, joints, gears), the two sets of contact arrays, the contact-key set
+	DW dw = [] { DW d = {}; d.cellSize = d.invCellSize = 1.0f; return d; }();
+#define X(T, name, count, keep, zeroNew) DevArray<T> name;
+	WORLD_ARRAYS_DW(X)
+	WORLD_ARRAYS_HOST(X)
+#undef X
 	DevArray<DState> d_state;
-	DevArray<float4> b_pos, b_pos0, b_vel, b_xf, b_mass, b_damp, b_force;
-	DevArray<uint32_t> b_flags;
-	DevArray<int> b_wake, b_rowDirty;
-	DevArray<float4> p_fat;
-	DevArray<int> p_body, p_shape, p_key, p_filter1;
-	DevArray<uint32_t> p_filter0;
-	DevArray<float2> p_mat;
-	DevArray<int> b_proxyHead, p_next, toiList, toiPos2c, toiDestroyList, toiNewList, b_toiGroup, toiGroups, toiGroupCount, toiGroupList, toiMoved, toiNew, toiParent, toiDomOf, toiDomRoot, toiDomCount, toiDomBase, toiDomFill, toiDomList, toiDomFailed, toiDomEvents;
-	DevArray<float4> toiHull;
-	DevArray<float4> snapBody, snapFat;
 	DevArray<ShapeRec> d_shapes;
+	DevArray<RevoluteJoint> d_joints;
+	DevArray<GearRec> d_gears;
 	DevArray<int4> c_ids[2];
 	DevArray<uint64_t> c_key[2];
 	DevArray<uint32_t> c_flags[2];
 	DevArray<float4> c_mat[2], c_man0[2], c_man1[2], c_imp[2];
 	DevArray<int4> c_man3[2];
 	DevArray<int> c_color[2], c_mgr[2];
-	DevArray<int4> li_ref;
 	DevArray<uint64_t> ht_keys;
-	DevArray<RevoluteJoint> d_joints, solveSnapJoints;
-	DevArray<GearRec> d_gears, solveSnapGears;
-	DevArray<float4> solveSnapBody, solveSnapImp; DevArray<uint32_t> solveSnapCFlags; // k_solver_snapshot (b2d_kernels_sweep_end.h)
-	DevArray<int> jadjStart, jadj, rootJointStart, rootJointCursor, lj_list, rootJointOkay;
 	std::vector<std::pair<int, int> > pendingFilter; // body pairs whose contacts must be re-filtered (new joint)
 	int nMouseJoints = 0;
 	size_t jadjBodies = (size_t)-1, jadjJoints = (size_t)-1; // what the device's per-body joint lists were last built for
 	std::vector<GearRec> gears;   // gear joints' own records, appended like joints (the device copy keeps the impulses)
 	size_t upGears = 0;
 	std::vector<JointEdit> jointEdits; // joints a setter changed since the last upload, in call order (queueJointEdit; uploadJointEdits)
-	DevArray<int> parent, rootSeed, rootBodies, rootContacts, rootJoints, rootIsland, deg, adjStart, adjCursor, adj;
-	DevArray<int2> adjSlot;
-	DevArray<int4> rootScanIn, rootScanOut;
-	DevArray<int> si_root, si_bodyStart, si_contactStart, si_wStart, si_maxLevel, si_bodies, si_contacts, si_level,
-		si_stack, si_lastLevel, b_slot, b_island, chunkFirst;
-	DevArray<int> li_bodies, li_contacts, li_roots, li_color, colorCount, colorStart, colorCursor, li_sorted;
-	DevArray<uint32_t> bodyClaim, rootPen, rootSleepMin;
-	DevArray<uint64_t> bodyColorMask, bodyActive, bodyRest;
-	DevArray<float4> b_posv;
-	DevArray<unsigned long long> evKey;
-	DevArray<int4> evInfo;
 	bool eventsOn = false;
 	std::vector<b2hip_contact_event> events; // of the last step, in delivery order
 	std::vector<b2hip_toi_callback> toiCallbacks; // listener calls of the last step's TOI sub-steps, in call order
-	DevArray<ToiLogRec> toiLog;
-	DevArray<int4> toiVerdict; // PreSolve answers for the TOI phase's log slots (DW::toiVerdict)
-	DevArray<int> uncolList, compactList, hubRowOf, hubList;
-	DevArray<float4> hubDelta, warmDelta;
-	DevArray<unsigned long long> hubMeta, hubFirst;
-	DevArray<int> rootDone;
-	DevArray<float> lc;
-	DevArray<int> moveBuf, gridCount, gridStart, gridCursor, gridItems, largeProxies, largeMoves;
-	DevArray<float4> gridFat;
-	DevArray<unsigned long long> arriveTree;
-	DevArray<uint64_t> pairKey, pairKey2;
-	DevArray<int2> pairProxy, pairProxy2;
-	DevArray<int> pairFirst, pairRank;
-	DevArray<int> scanTmp, radixHist, radixHistScan, keepFlag, keepScan;
-	DevArray<int4> scanTmp4;
 	// batched queries (b2hip_api_query.h): the batch and its results on the device, a pinned staging buffer for the copies,
 	// scan scratch of their own (the step's scan context reports a look-back failure into Counters::overflow); grown on demand
 	DevArray<float4> qIn;
@@ -300,7 +508,7 @@ struct b2hip_world
 	DevArray<float4> jbOut;
 	std::vector<uint32_t> jbSeen;
 	uint32_t jbEpoch = 0;
-	ScanFlags qScan;
+	ScanFlags qScan = {};
 	void* qPinned = nullptr;
 	size_t qPinnedBytes = 0;
 	void* shardComm = nullptr;   // ncclComm_t of a connected sharded world (b2hip_shard_connect)
@@ -309,23 +517,20 @@ struct b2hip_world
 	bool shardLoopback = false;  // B2HIP_SHARD_LOOPBACK=1: a communicator of ONE rank still runs export -> ncclAllGather -> import (self-test on a one-GPU box)
 	// spatial ownership (b2d_kernels_spatial.h; b2hip_shard_spatial)
 	bool spatial = false;
-	DevArray<uint8_t> b_owner, spNewOwner, spAwake;
 	bool spFullRows = false;       // B2HIP_SHARD_FULL_ROWS=1 / b2hip_shard_full_rows: every rank holds every body's current row
 	int spRowCap = 1024, spProxyCap = 4096;
 	int spIdle[6] = {0, 0, 0, 0, 0, 0}; // exchanges in a row in which a capacity was four times what any rank needed (spCapDecay) // lean E1: records per rank (grown alike on every rank when a header says so)
-	DevArray<int> spStraddle, spCount, spTarget, spSend, spRecv;
+	DevArray<int> spSend, spRecv;
 	std::vector<uint8_t> spOwners; // the owner table as the host last knew it (assignment; refreshed after every resolution)
 	bool spOwnersDirty = false;    // owners assigned / bodies created since the table was uploaded
 	float spBounds[SHARD_MAX_RANKS + 1] = {0}; // strips along x the owners were dealt by (bodies created later fall into them)
 	b2hip_all_gather_fn gatherFn = nullptr; // the caller's all-gather (gloo, tests); null with a connected RCCL communicator
 	void* gatherUser = nullptr;
-	int* spHost = nullptr;          // pinned staging of the caller's all-gather
+	PinnedBuf<int> spHost;          // staging of the caller's all-gather
 	const int* spSendWiped = nullptr; // == spSend.p: its header has been wiped by the last import launch (spPrepareSend)
-	int* spHdrHost = nullptr;       // pinned: [0] sequence number, [1] extra word, [2..] the headers of all ranks' slabs (spReadHeaders)
-	int* spHdrDev = nullptr;
+	PinnedBuf<int> spHdrHost;       // mapped: [0] sequence number, [1] extra word, [2..] the headers of all ranks' slabs (spReadHeaders)
 	int spHdrSeq = 0;
-	int* spOwnHost = nullptr;       // pinned: the packed rows of this rank's bodies (id + b2hip_body_state), written by k_end_step
-	int* spOwnDev = nullptr;        // ... its device address
+	PinnedBuf<int> spOwnHost;       // mapped: the packed rows of this rank's bodies (id + b2hip_body_state), written by k_end_step
 	size_t spOwnCapRows = 0;
 	size_t spHostWords = 0;
 	int spPairCap = 2048, spToiBodyCap = 256, spToiProxyCap = 512; // (records per rank; grown alike on every rank when a header says so)
@@ -335,8 +540,6 @@ struct b2hip_world
 	int spContactsBeforeToi = 0, spToiOrderBefore = 0, spTailCap = 64;
 	int spToiUnsafe = 0;            // this rank's Counters::toiUnsafe as its E4 header showed it
 	bool spToiSettled = false;      // this step's phase has been through its fallback already
-	DevArray<int4> spTailKey;
-	DevArray<int2> spVirt;          // body pairs a TOI event would have joined over an ownership boundary (k_sp_tail_pairs)
 	// measurement hook (b2hip_shard_tape): the results of this rank's collectives kept in device memory / taken from another
 	// world's tape instead of a collective - one rank of a sharded world stepped alone on one GPU (tools/gpu_spatial_share.py)
 	bool spTapeRecord = false;
@@ -345,17 +548,12 @@ struct b2hip_world
 	size_t spTapeCursor = 0;
 	long long spToiRedos = 0;
 	size_t spUp = 0;                // bodies the device's owner table covers
-	DevArray<int> scanFlags;     // status words of the single-pass scans (b2d_scan.h)
-	ScanFlags scanCtx;           // ... with their epoch and the abort word (refreshed by ensureCapacity)
-	DevArray<unsigned> radixCounts, radixGroups; // status words of the one-launch radix passes (b2d_scan.h)
-	DevArray<int> radixGlobalHist; // ... and the two buffers of the sorts' global digit histograms
-	RadixStatus radixCtx;        // ... with their tag (refreshed by ensureCapacity)
+	ScanFlags scanCtx = {};      // scanFlags with their epoch and the abort word (refreshed by ensureCapacity)
+	RadixStatus radixCtx = {};   // radixCounts / radixGroups / radixGlobalHist with their tag (refreshed by ensureCapacity)
 	bool sortOnepass = true;     // B2HIP_SORT_ONEPASS=0: every radix pass as three launches (histogram, scan, scatter)
 	long long statSorts = 0, statSortsOnepass = 0; // radix sorts queued since the world was created / of them in the one-launch form (b2hip_debug_read 22)
-	DevArray<float> stateOut;
-	DevArray<int> gridBar;       // grid barrier state of the persistent solver
-	int dfEpoch;
-	bool noSideStream, profileDetail;
+	int dfEpoch = 0;
+	bool noSideStream = false, profileDetail = false;
 	int collideStage = -1;       // B2HIP_COLLIDE_STAGE=0 / 1: never / always stage the shape records through LDS (default: by the record count)
 	int solidRoundsEnv = 0;      // B2HIP_SOLID_ROUNDS=1 / 2 / 4 / 8: the tile of the island build's passes over the contacts (x 256 contacts), else by the contact count
 	int collideSplitEnv = -1;    // B2HIP_COLLIDE_SPLIT=0 / 1: k_collide with the TOI-order replay inside / as a launch of its own (four waves per SIMD), else by the contact count
@@ -363,19 +561,15 @@ struct b2hip_world
 	bool collideCompactOn = true;  // B2HIP_COLLIDE_COMPACT=0: never (the scan of the keep flags and k_compact_contacts behind every narrow phase)
 	int collideChunk = 256;        // contacts per workgroup of that form (B2HIP_TEST_COLLIDE_CHUNK: fewer, so that a small world has many chunks and groups of chunks)
 	bool contactsKnown = false;    // h_dstate holds the contact count and the TOI slot count as they are on the device: true behind a step's last read-back and behind applyEditOps', false once a narrow phase or a pair update is queued
-	DevArray<unsigned> collideCounts, collideGroups; // its status words, a chunk's count / a group's sum each
-	unsigned collideEpoch = 0;     // tag of its last launch (16 bits, never 0)
+	unsigned collideEpoch = 0;     // tag of its last launch (16 bits, never 0; the status words: collideCounts, collideGroups)
 	long long statCollideCompact = 0; // narrow phases that took that form since the world was created (b2hip_debug_read 24)
 	bool collideUniOff = false;  // B2HIP_COLLIDE_UNI=0: k_collide reads every shape record from memory (no staged pair of records)
 	int collideSortEnv = -1;     // B2HIP_COLLIDE_SORT=0 / 1: k_collide never / always sorts the contacts of a tile by shape-pair class in LDS
 	hipStream_t stream2 = nullptr; // small-island solver beside the large-island one
 	hipEvent_t evFork = nullptr, evJoin = nullptr;
-	DevArray<int> consts; // [0] nBodies, [1] gridSize, [2] radix hist count, [3] sorted-pair count
 	DevArray<unsigned long long> filterPairs; // sorted body-pair keys of the joints created / destroyed since the last step
 	std::vector<int> nonStatic;       // the reference's m_nonStaticBodies: body ids in its order (island seed order)
 	bool orderDirty = false;
-	DevArray<int> b_order, orderBody;
-	DevArray<int> bigRoots;           // sharded worlds: roots of this step's big islands
 	// edits of existing fixtures / contacts between steps (b2d_kernels_edit.h)
 	std::vector<int2> editOps;        // queued contact-array ops, in call order
 	std::vector<int> proxyEdits;      // fixtures whose device proxy row (filter words, body) must be rewritten
@@ -392,15 +586,7 @@ struct b2hip_world
 	void* preSolveUser = nullptr;
 	bool postSolveOn = false;
 	std::vector<b2hip_contact_impulse> postSolve; // of the last step, in delivery order
-	DevArray<float4> pre_o0, pre_o1, pre_oimp;
-	DevArray<int4> pre_o3;
-	DevArray<PreSolveRec> preRecs;
-	DevArray<PostSolveRec> postRecs;
-	DevArray<int> filterList, hostList; // hostList: indices uploaded by the host (contacts to disable / reject, pairs to drop)
 	// block partition of the large islands (b2d_kernels_solve_blocks.h)
-	DevArray<int> b_adoptStage;
-	DevArray<int> b_blk1, b_adopt, blkRows, blkRowStart, blkCursor, blkBodyStart, blkBodies, rowColor, blkBodyCount, blkBodyCursor;
-	DevArray<float4> b_cutv;
 	int blocksMaxWG = 0;         // co-resident workgroups of k_solve_blocks on this device (0 = do not use it)
 	int sweepMaxWG[3] = { 0, 0, 0 }; // ... of k_blocks_sweep<256 / 512 / 1024>
 	int hubWaves = 8;            // waves of k_large_hub (B2HIP_HUB_WAVES=1: one)
@@ -425,8 +611,7 @@ struct b2hip_world
 	bool hubOrderAll = false;    // B2HIP_HUB_ORDER=1: ... ordered also where every hub row is swept lane after lane (B2HIP_HUB_WIDE=0 / B2HIP_HUB_SERIAL=1: comparison runs)
 	bool recoverOn = true;       // a timed-out wait between workgroups of the large-island solver is recovered from (saved state back, the
 	                             // solve once more launch by launch; B2HIP_NO_RECOVER=1: the step fails as in round 5)
-	int* h_solverWord = nullptr; // mapped host memory: [0] the overflow word behind the solver, [1] the publication's number (k_solver_status)
-	int* d_solverWord = nullptr;
+	PinnedBuf<int> h_solverWord; // mapped, 16 words: [0] the overflow word behind the solver, [1] the publication's number (k_solver_status)
 	int solverSeq = 0;
 	int colorRecoveries = 0;     // steps whose colouring ran out of colours / of rounds and went on (swept in order / finished by the grid-wide rounds)
 	int solverRecoveries = 0;    // solves run a second time so far (b2hip_get_counters: solver_recoveries)
@@ -473,17 +658,14 @@ struct b2hip_world
 		int nColors = 0, hasHubs = 0, hasJoints = 0, hubBuildOne = 0, useSweepEnd = 0, leftoverApart = 0;
 	} planRecord;
 
-	// pinned host buffers
-	float* h_state;             // pinned, coherent: k_end_step writes the read-back into it (d_hstate = its device address)
-	float* d_hstate = nullptr;
+	// pinned host buffers (mapped and coherent where a kernel writes what the host polls: PinnedBuf::dev is the kernel's address)
+	PinnedBuf<float> h_state;    // mapped: k_end_step writes the read-back into it
 	int stateSeq = 0;            // sequence number of the last read-back asked for (awaitState)
-	size_t h_stateCap;
-	DState* h_dstate;
-	DState* h_pub2 = nullptr;    // ... and where k_color_small publishes the state behind the colouring (a buffer and a count of its own: pubSeq2)
-	DState* d_pub2 = nullptr;
+	size_t h_stateCap = 0;
+	PinnedBuf<DState> h_dstate;
+	PinnedBuf<DState> h_pub2;    // ... and where k_color_small publishes the state behind the colouring (a buffer and a count of its own: pubSeq2)
 	int pubSeq2 = 0;
-	DState* h_pub = nullptr;     // where k_block_census publishes the island census (pinned, coherent); polled by awaitCensus
-	DState* d_pub = nullptr;     // ... its device address
+	PinnedBuf<DState> h_pub;     // mapped: where k_block_census publishes the island census; polled by awaitCensus
 	int pubSeq = 0;
 	bool noCensusPoll = false;   // B2HIP_NO_CENSUS_POLL=1: copy + stream synchronisation instead (for comparison)
 	bool noStatePoll = false;    // B2HIP_NO_STATE_POLL=1: the same for the read-back at the end of the step
@@ -505,14 +687,14 @@ struct b2hip_world
 	std::mutex rowsMutex;
 	bool blocksThisStep = false; // the large islands of this step went through k_solve_blocks
 
-	Counters last;        // counters of the last completed step
-	int lastContacts;
-	float profile[13];
-	hipEvent_t ev[13];
-	float solverMs;
-	double solverBytes;
-	int solverConstraints, solverBodies;
-	int forceLarge;
+	Counters last = {};   // counters of the last completed step
+	int lastContacts = 0;
+	float profile[13] = {};
+	hipEvent_t ev[13] = {};
+	float solverMs = 0.0f;
+	double solverBytes = 0.0;
+	int solverConstraints = 0, solverBodies = 0;
+	int forceLarge = 0;
 	// optional per-launch timing of the dominant solver kernel
 	size_t pairCapHint = 0; // pair-buffer size asked for after an overflow (growPairBuffers)
 	int constsUploaded[2] = { -1, -1 };
@@ -526,20 +708,20 @@ struct b2hip_world
 	// and leaves the step open; the calls that follow run Collide and the next event but no island solve, until no event is left
 	bool stepComplete = true;  // b2World::m_stepComplete
 	bool stepSolves = true;    // this call runs Solve (it started from a complete step)
-	bool kernelTimingLaunches, colorSmallPending;
-	int hubSteps;
-	bool debugTrace;                                   // B2HIP_TRACE=1: hash the body state after every solver stage
+	bool kernelTimingLaunches = false, colorSmallPending = false;
+	int hubSteps = 0;
+	bool debugTrace = false;                           // B2HIP_TRACE=1: hash the body state after every solver stage
 	std::vector<std::pair<std::string, uint64_t> > trace;
 	DevArray<float4> dbgPreVel, dbgVel;
 	DevArray<int> dbgLi;
-	int kernelTiming;
-	long long ktUnitsA, ktUnitsB; // units behind the bandwidth kernels' byte counts (set by b2hip_set_kernel_timing_units)
+	int kernelTiming = 0;
+	long long ktUnitsA = 0, ktUnitsB = 0; // units behind the bandwidth kernels' byte counts (set by b2hip_set_kernel_timing_units)
 	std::vector<hipEvent_t> ktEvents;
-	int ktUsed;          // events recorded this step (pairs)
-	int ktKind;          // 0 none, 1 k_large_velocity, 2 k_solve_small, 4 k_solve_blocks, 5 - 7 (ktBracket), 8 the solver family
-	float ktMs;
-	int ktLaunches;
-	double ktBytes;
+	int ktUsed = 0;      // events recorded this step (pairs)
+	int ktKind = 0;      // 0 none, 1 k_large_velocity, 2 k_solve_small, 4 k_solve_blocks, 5 - 7 (ktBracket), 8 the solver family
+	float ktMs = 0.0f;
+	int ktLaunches = 0;
+	double ktBytes = 0.0;
 };
 
 // Every entry point that touches the device runs with the world's device current and puts the caller's device back
@@ -1054,37 +1236,53 @@ static void readSwitches(b2hip_world* w)
 	d.hubWide = (w->sweepEnd && !d.hubSerial && envInt("B2HIP_HUB_WIDE", 1) != 0) ? 1 : 0;
 }
 
+// What ensureCapacity's counts are made of, worked out once per call: WorldSizes z = { w, needContacts }.
+struct WorldSizes
+{
+	const b2hip_world* w;
+	size_t needContacts;
+	size_t nb = std::max<size_t>(w->bodies.size(), 1), np = std::max<size_t>(w->fixtures.size(), 1);
+	size_t nj = std::max<size_t>(w->joints.size(), 1), ng = std::max<size_t>(w->gears.size(), 1);
+	size_t capPairs = std::max<size_t>(std::max<size_t>(8 * np + 4096, w->pairKey.cap), w->pairCapHint);
+	size_t capContacts = std::max<size_t>(needContacts + capPairs, 1024); // the contact arrays' room asked for ...
+	size_t cc = w->c_ids[0].capFor(capContacts);                          // ... and the (power of two) capacity they get
+	size_t gridSize = (size_t)nextPow2(2 * np);
+	size_t maxScanN = std::max(std::max(nb + 2, gridSize + 2), std::max(cc + 2, capPairs + 2));
+	size_t radixTiles = capPairs / RADIX_TILE + 2;
+	// tiles / chunks the one-launch radix passes / k_collide<0, false, true> have status words for (0: switched off)
+	size_t onepassTiles = w->sortOnepass ? std::min<size_t>(radixTiles, RADIX_ONEPASS_MAX_TILES) : 0;
+	size_t collideChunks = w->collideCompactOn ? cc / (size_t)w->collideChunk + 2 : 0;
+	// the listener arrays: contact-sized only while the callback that needs them is installed
+	size_t nPre = hasPreSolve(w) ? cc : 1, nPost = w->postSolveOn ? cc : 1, nFil = hasFilter(w) ? cc : 1;
+};
+
 // Size every buffer for the current topology and a contact / pair budget; refresh the kernarg block.
 static int ensureCapacity(b2hip_world* w, size_t needContacts)
 {
 	hipStream_t s = w->stream;
-	const size_t nb = std::max<size_t>(w->bodies.size(), 1);
-	const size_t np = std::max<size_t>(w->fixtures.size(), 1);
+	const WorldSizes z = { w, needContacts };
+	const size_t nb = z.nb;
+	DW& d = w->dw;
 	int rc = 0;
 #define ENS(arr, n) do { rc = w->arr.ensure((n), s); if (rc) return rc; } while (0)
 	ENS(d_state, 1);
-	ENS(b_pos, nb); ENS(b_pos0, nb); ENS(b_vel, nb); ENS(b_xf, nb); ENS(b_mass, nb); ENS(b_damp, nb); ENS(b_force, nb);
-	ENS(b_flags, nb); ENS(b_wake, nb); ENS(b_rowDirty, nb); ENS(b_order, nb); ENS(orderBody, nb); ENS(bigRoots, SHARD_BIG_MAX);
-	ENS(p_fat, np); ENS(p_body, np); ENS(p_shape, np); ENS(p_key, np); ENS(p_filter0, np); ENS(p_filter1, np); ENS(p_mat, np);
-	ENS(b_proxyHead, nb); ENS(p_next, np);
 	ENS(d_shapes, std::max<size_t>(w->shapes.size(), 1));
-	ENS(d_joints, std::max<size_t>(w->joints.size(), 1));
-	ENS(d_gears, std::max<size_t>(w->gears.size(), 1));
-	ENS(solveSnapJoints, w->recoverOn ? std::max<size_t>(w->joints.size(), 1) : 1); ENS(solveSnapGears, w->recoverOn ? std::max<size_t>(w->gears.size(), 1) : 1);
-	ENS(jadjStart, nb + 2); ENS(jadj, 2 * w->joints.size() + 2); ENS(rootJointStart, nb + 2); ENS(rootJointCursor, nb);
-	ENS(lj_list, w->joints.size() + 2); ENS(rootJointOkay, nb);
-	const size_t capPairs = std::max<size_t>(std::max<size_t>(8 * np + 4096, w->pairKey.cap), w->pairCapHint);
-	const size_t capContacts = std::max<size_t>(needContacts + capPairs, 1024);
+	ENS(d_joints, z.nj);
+	ENS(d_gears, z.ng);
+	d.shapes = w->d_shapes.p; d.joints = w->d_joints.p; d.gears = w->d_gears.p;
 	for (int k = 0; k < 2; ++k)
 	{
-		ENS(c_ids[k], capContacts); ENS(c_key[k], capContacts); ENS(c_flags[k], capContacts); ENS(c_mat[k], capContacts);
-		ENS(c_man0[k], capContacts); ENS(c_man1[k], capContacts); ENS(c_imp[k], capContacts); ENS(c_man3[k], capContacts);
-		ENS(c_color[k], capContacts); ENS(c_mgr[k], capContacts);
+		ENS(c_ids[k], z.capContacts); ENS(c_key[k], z.capContacts); ENS(c_flags[k], z.capContacts); ENS(c_mat[k], z.capContacts);
+		ENS(c_man0[k], z.capContacts); ENS(c_man1[k], z.capContacts); ENS(c_imp[k], z.capContacts); ENS(c_man3[k], z.capContacts);
+		ENS(c_color[k], z.capContacts); ENS(c_mgr[k], z.capContacts);
+		d.ca[k].ids = w->c_ids[k].p; d.ca[k].key = w->c_key[k].p; d.ca[k].flags = w->c_flags[k].p; d.ca[k].mat = w->c_mat[k].p;
+		d.ca[k].man0 = w->c_man0[k].p; d.ca[k].man1 = w->c_man1[k].p; d.ca[k].imp = w->c_imp[k].p; d.ca[k].man3 = w->c_man3[k].p;
+		d.ca[k].color = w->c_color[k].p; d.ca[k].mgr = w->c_mgr[k].p;
 	}
-	const size_t cc = w->c_ids[0].cap; // actual (power of two) capacity
+#undef ENS
 	// hash set: at most 50 % load
 	{
-		size_t want = (size_t)nextPow2(2 * cc);
+		size_t want = (size_t)nextPow2(2 * z.cc);
 		if (w->ht_keys.cap < want)
 		{
 			const bool had = w->ht_keys.cap != 0;
@@ -1095,162 +1293,59 @@ static int ensureCapacity(b2hip_world* w, size_t needContacts)
 			if (had) HIP_TRY(hipMemcpyAsync(&w->d_state.p->c.ksStale, &one, sizeof(int), hipMemcpyHostToDevice, s));
 		}
 	}
-	ENS(parent, nb); ENS(rootSeed, nb); ENS(rootBodies, nb); ENS(rootContacts, nb); ENS(rootJoints, nb); ENS(rootIsland, nb);
-	ENS(deg, nb + 1); ENS(adjStart, nb + 2); ENS(adjCursor, nb); ENS(adj, 2 * cc); ENS(adjSlot, cc);
-	ENS(rootScanIn, nb + 1); ENS(rootScanOut, nb + 2);
-	ENS(si_root, nb + 1); ENS(si_bodyStart, nb + 2); ENS(si_contactStart, nb + 2); ENS(si_wStart, nb + 2); ENS(si_maxLevel, nb + 1);
-	ENS(si_bodies, nb); ENS(si_contacts, cc); ENS(si_level, cc); ENS(si_stack, nb); ENS(si_lastLevel, nb);
-	ENS(b_slot, nb); ENS(b_island, nb); ENS(chunkFirst, (nb + cc) / (TINY_CHUNK_LANES / 2) + 4);
-	ENS(li_bodies, nb); ENS(li_contacts, cc); ENS(li_roots, nb); ENS(li_color, cc);
-	ENS(colorCount, cc + 2 + COLOR_SLOT_PADDED * COLOR_SLOT_STRIDE); ENS(colorStart, cc + 2); ENS(colorCursor, cc + 2 + COLOR_SLOT_PADDED * COLOR_SLOT_STRIDE); ENS(li_sorted, cc); ENS(li_ref, cc); // (colorSlot: the first 65 colour counters on a line each)
-	ENS(bodyClaim, nb); ENS(bodyColorMask, nb); ENS(bodyActive, nb); ENS(bodyRest, nb); ENS(b_posv, nb); ENS(evKey, cc); ENS(evInfo, cc); ENS(uncolList, COLOR_SMALL_MAX); ENS(compactList, COLOR_SMALL_MAX); ENS(hubRowOf, cc); ENS(hubList, cc); ENS(hubDelta, cc); ENS(hubMeta, 8); ENS(hubFirst, nb); ENS(solveSnapBody, w->recoverOn ? 6 * nb : 1); ENS(solveSnapImp, w->recoverOn ? cc : 1); ENS(solveSnapCFlags, w->recoverOn ? cc : 1); ENS(rootPen, ROOT_PEN_SLOTS * nb); ENS(rootDone, nb); ENS(rootSleepMin, nb);
-	if (w->lc.cap < (size_t)LC_WORDS * cc)
-	{
-		rc = w->lc.ensure((size_t)LC_WORDS * cc, s, false, false);
-		if (rc) return rc;
-	}
-	if (w->warmDelta.cap < 4 * cc)
-	{
-		rc = w->warmDelta.ensure(4 * cc, s, false, false); // (per-step scratch: k_large_init -> k_large_warm)
-		if (rc) return rc;
-	}
-	ENS(moveBuf, 2 * np + 64);
-	const size_t gridSize = (size_t)nextPow2(2 * np);
-	ENS(gridCount, gridSize); ENS(gridStart, gridSize + 2); ENS(gridCursor, gridSize); ENS(gridItems, np); ENS(gridFat, np); ENS(arriveTree, (size_t)ARRIVE_SITES * TREE_WORDS); ENS(largeProxies, np); ENS(largeMoves, 2 * np + 64);
-	ENS(pairKey, capPairs); ENS(pairKey2, capPairs); ENS(pairProxy, capPairs); ENS(pairProxy2, capPairs);
-	ENS(pairFirst, capPairs + 1); ENS(pairRank, capPairs + 2);
-	const size_t maxScanN = std::max(std::max(nb + 2, gridSize + 2), std::max(cc + 2, capPairs + 2));
-	const size_t radixTiles = capPairs / RADIX_TILE + 2;
-	ENS(radixHist, RADIX_DIGITS * radixTiles + 2); ENS(radixHistScan, RADIX_DIGITS * radixTiles + 4);
-	ENS(scanTmp, 3 * (std::max(maxScanN, RADIX_DIGITS * radixTiles) / SCAN_TILE + 8));
-	ENS(scanTmp4, 3 * (maxScanN / SCAN_TILE + 8));
-	ENS(scanFlags, std::max(maxScanN, RADIX_DIGITS * radixTiles) / SCAN_TILE + 8);
-	// (one-launch radix passes: status words for the pair buffers' tiles up to RADIX_ONEPASS_MAX_TILES - a sort over more takes
-	// the three-launch form; a grown array starts from zeroed words under the running tag, which no word carries yet)
-	const size_t onepassTiles = w->sortOnepass ? std::min<size_t>(radixTiles, RADIX_ONEPASS_MAX_TILES) : 0;
-	if (onepassTiles)
-	{
-		rc = w->radixCounts.ensure(onepassTiles * RADIX_DIGITS, s, false); if (rc) return rc;
-		rc = w->radixGroups.ensure((onepassTiles / RADIX_GROUP + 1) * RADIX_DIGITS, s, false); if (rc) return rc;
-		ENS(radixGlobalHist, 2 * RADIX_MAX_PASSES * RADIX_DIGITS);
-	}
-	ENS(keepFlag, cc + 1); ENS(keepScan, cc + 2);
-	if (w->collideCompactOn)
-	{
-		// (status words of k_collide<0, false, true> for every chunk the contact array can hold; a grown array starts from zeroed words
-		// under the running tag, which no word carries yet)
-		const size_t chunks = cc / (size_t)w->collideChunk + 2;
-		rc = w->collideCounts.ensure(chunks, s, false); if (rc) return rc;
-		rc = w->collideGroups.ensure(chunks / COLLIDE_GROUP + 2, s, false); if (rc) return rc;
-	}
-	ENS(toiList, cc); ENS(toiPos2c, cc); ENS(toiDestroyList, cc); ENS(toiNewList, TOI_NEW_LIST_MAX);
-	ENS(b_toiGroup, nb); ENS(toiGroups, nb); ENS(toiGroupCount, std::min<size_t>(nb, TOI_GROUPS_MAX)); ENS(toiGroupList, std::min<size_t>(nb, TOI_GROUPS_MAX) * CHAIN_ADJ_MAX); ENS(toiMoved, TOI_MOVED_ALL_MAX); ENS(toiNew, 8 * TOI_NEWPAIR_MAX); ENS(toiParent, nb); ENS(toiDomOf, nb); ENS(toiDomRoot, TOI_DOMAINS_MAX); ENS(toiDomCount, TOI_DOMAINS_MAX); ENS(toiDomBase, TOI_DOMAINS_MAX); ENS(toiDomFill, TOI_DOMAINS_MAX); ENS(toiDomFailed, TOI_DOMAINS_MAX); ENS(toiDomEvents, TOI_DOMAINS_MAX); ENS(toiDomList, cc); ENS(toiHull, np); ENS(snapBody, 5 * nb); ENS(snapFat, np);
-	{
-		// listener bridge buffers: contact-sized only while the callback that needs them is installed
-		const size_t nPre = hasPreSolve(w) ? cc : 1, nPost = w->postSolveOn ? cc : 1, nFil = hasFilter(w) ? cc : 1;
-		ENS(pre_o0, nPre); ENS(pre_o1, nPre); ENS(pre_oimp, nPre); ENS(pre_o3, nPre); ENS(preRecs, nPre);
-		ENS(postRecs, nPost); ENS(filterList, nFil);
-		ENS(toiLog, listenerOn(w) && w->def.continuous ? cc : 1);
-		ENS(toiVerdict, hasPreSolve(w) && w->def.continuous ? cc : 1);
-		ENS(hostList, std::max<size_t>(std::max(4 * nPre, nFil), hasFilter(w) ? capPairs : 1)); // (PreSolve material edits: 4 words each)
-	}
-	ENS(b_blk1, nb); ENS(b_adopt, nb); ENS(b_adoptStage, 3 * nb); ENS(blkRows, (size_t)(MAX_BLOCKS + 2) * BLK_SLOT); ENS(blkRowStart, MAX_BLOCKS + 2); ENS(blkCursor, (size_t)(MAX_BLOCKS + 2) * BLK_SLOT); ENS(blkBodyCount, (size_t)(MAX_BLOCKS + 2) * BLK_SLOT); ENS(blkBodyCursor, (size_t)(MAX_BLOCKS + 2) * BLK_SLOT);
-	ENS(blkBodyStart, MAX_BLOCKS + 2); ENS(blkBodies, nb); ENS(rowColor, cc); ENS(b_cutv, nb);
-	ENS(b_owner, w->spatial ? nb : 1); ENS(spNewOwner, w->spatial ? nb : 1); ENS(spAwake, w->spatial ? nb : 1); ENS(spStraddle, w->spatial ? std::max<size_t>(w->spStraddle.cap, 4096) : 1);
-	ENS(spCount, w->spatial ? (size_t)SP_RESOLVE_MAX * SHARD_MAX_RANKS : 1); ENS(spTarget, w->spatial ? SP_RESOLVE_MAX : 1);
-	ENS(spTailKey, w->spatial ? capContacts : 1); ENS(spVirt, w->spatial ? SP_TAIL_MAX + 1 : 1);
-	ENS(stateOut, 12 * nb + sizeof(DState) / sizeof(float) + 4); // (+ the counters, behind the rows: one copy to the host per step)
-	ENS(consts, 16);
-	ENS(gridBar, 32);
-#undef ENS
-	w->scanCtx.words = w->scanFlags.p; // (a grown array keeps its words: the epoch goes on)
+	d.ht_keys = w->ht_keys.p;
+	// the two tables: every array sized, then DW's pointers set from the arrays
+#define X(T, name, count, keep, zeroNew) if ((rc = w->name.ensure((count), s, (keep), (zeroNew)))) return rc;
+	WORLD_ARRAYS_DW(X)
+	WORLD_ARRAYS_HOST(X)
+#undef X
+#define X(T, name, count, keep, zeroNew) d.name = w->name.p;
+	WORLD_ARRAYS_DW(X)
+#undef X
+	w->scanCtx.words = w->scanFlags.p;
 	w->scanCtx.count = w->scanFlags.cap;
 	w->scanCtx.abortWord = &w->d_state.p->c.overflow;
 	w->radixCtx.counts = w->radixCounts.p; w->radixCtx.countsCap = w->radixCounts.cap;
 	w->radixCtx.groups = w->radixGroups.p; w->radixCtx.groupsCap = w->radixGroups.cap;
 	w->radixCtx.hist = w->radixGlobalHist.p;
-	w->radixCtx.maxTiles = w->sortOnepass ? (int)std::min<size_t>(std::min<size_t>(w->radixCounts.cap / RADIX_DIGITS, (w->radixGroups.cap / RADIX_DIGITS) * RADIX_GROUP), RADIX_ONEPASS_MAX_TILES) : 0;
+	w->radixCtx.maxTiles = !w->sortOnepass ? 0 : (int)std::min<size_t>(
+		std::min<size_t>(w->radixCounts.cap / RADIX_DIGITS, (w->radixGroups.cap / RADIX_DIGITS) * RADIX_GROUP), RADIX_ONEPASS_MAX_TILES);
 	w->radixCtx.abortWord = &w->d_state.p->c.overflow;
 	if (w->h_stateCap < 12 * nb + sizeof(DState) / sizeof(float) + 4)
 	{
 		// (the rows of the last read-back are the host's mirror of every body it has not edited: they move along)
 		ensureRows(w);
-		float* old = w->h_state;
-		w->h_state = nullptr;
-		w->h_stateCap = 12 * nb * 2 + sizeof(DState) / sizeof(float) + 4;
-		HIP_TRY(hipHostMalloc((void**)&w->h_state, w->h_stateCap * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
-		HIP_TRY(hipHostGetDevicePointer((void**)&w->d_hstate, w->h_state, 0));
-		if (old)
-		{
-			memcpy(w->h_state, old, w->stateCount * 10 * sizeof(float));
-			(void)hipHostFree(old);
-		}
+		const size_t cap = 12 * nb * 2 + sizeof(DState) / sizeof(float) + 4;
+		PinnedBuf<float> grown;
+		rc = grown.alloc(cap, hipHostMallocMapped | hipHostMallocCoherent);
+		if (rc) return rc;
+		if (w->h_state) memcpy(grown, w->h_state, w->stateCount * 10 * sizeof(float));
+		w->h_state.swap(grown); // (which takes the old buffer away with it)
+		w->h_stateCap = cap;
 	}
 
-	DW& d = w->dw;
 	d.st = w->d_state.p;
 	d.nBodies = (int)w->bodies.size();
 	d.nProxies = (int)w->fixtures.size();
 	d.nJoints = (int)w->joints.size();
 	d.nShapes = (int)w->shapes.size();
-	d.capContacts = (int)cc;
+	d.capContacts = (int)z.cc;
 	d.capPairs = (int)w->pairKey.cap;
 	d.capMoves = (int)w->moveBuf.cap;
 	d.htMask = (uint32_t)(w->ht_keys.cap - 1);
-	d.gridMask = (uint32_t)(gridSize - 1);
-	d.b_pos = w->b_pos.p; d.b_pos0 = w->b_pos0.p; d.b_vel = w->b_vel.p; d.b_xf = w->b_xf.p; d.b_mass = w->b_mass.p;
-	d.b_damp = w->b_damp.p; d.b_force = w->b_force.p; d.b_flags = w->b_flags.p; d.b_wake = w->b_wake.p; d.b_rowDirty = w->b_rowDirty.p;
-	d.b_order = w->b_order.p; d.orderBody = w->orderBody.p; d.bigRoots = w->bigRoots.p;
-	d.p_fat = w->p_fat.p; d.p_body = w->p_body.p; d.p_shape = w->p_shape.p; d.p_key = w->p_key.p;
-	d.p_filter0 = w->p_filter0.p; d.p_filter1 = w->p_filter1.p; d.p_mat = w->p_mat.p; d.shapes = w->d_shapes.p;
-	for (int k = 0; k < 2; ++k)
-	{
-		d.ca[k].ids = w->c_ids[k].p; d.ca[k].key = w->c_key[k].p; d.ca[k].flags = w->c_flags[k].p; d.ca[k].mat = w->c_mat[k].p;
-		d.ca[k].man0 = w->c_man0[k].p; d.ca[k].man1 = w->c_man1[k].p; d.ca[k].imp = w->c_imp[k].p; d.ca[k].man3 = w->c_man3[k].p;
-		d.ca[k].color = w->c_color[k].p; d.ca[k].mgr = w->c_mgr[k].p;
-	}
-	d.ht_keys = w->ht_keys.p;
-	d.joints = w->d_joints.p; d.solveSnapJoints = w->solveSnapJoints.p; d.solveSnapGears = w->solveSnapGears.p; d.solveSnapBody = w->solveSnapBody.p; d.solveSnapImp = w->solveSnapImp.p; d.solveSnapCFlags = w->solveSnapCFlags.p;
-	d.gears = w->d_gears.p;
-	d.jadjStart = w->jadjStart.p; d.jadj = w->jadj.p; d.rootJointStart = w->rootJointStart.p;
-	d.rootJointCursor = w->rootJointCursor.p; d.lj_list = w->lj_list.p; d.rootJointOkay = w->rootJointOkay.p;
-	d.parent = w->parent.p; d.rootSeed = w->rootSeed.p; d.rootBodies = w->rootBodies.p; d.rootContacts = w->rootContacts.p;
-	d.rootJoints = w->rootJoints.p; d.rootScanIn = w->rootScanIn.p; d.rootScanOut = w->rootScanOut.p; d.rootIsland = w->rootIsland.p;
-	d.deg = w->deg.p; d.adjStart = w->adjStart.p; d.adjCursor = w->adjCursor.p; d.adj = w->adj.p; d.adjSlot = w->adjSlot.p;
-	d.si_root = w->si_root.p; d.si_bodyStart = w->si_bodyStart.p; d.si_contactStart = w->si_contactStart.p; d.si_wStart = w->si_wStart.p;
-	d.si_maxLevel = w->si_maxLevel.p; d.si_bodies = w->si_bodies.p; d.si_contacts = w->si_contacts.p; d.si_level = w->si_level.p;
-	d.si_stack = w->si_stack.p; d.si_lastLevel = w->si_lastLevel.p; d.b_slot = w->b_slot.p; d.b_island = w->b_island.p;
-	d.chunkFirst = w->chunkFirst.p;
-	d.li_bodies = w->li_bodies.p; d.li_contacts = w->li_contacts.p; d.li_roots = w->li_roots.p; d.li_color = w->li_color.p;
-	d.colorCount = w->colorCount.p; d.colorStart = w->colorStart.p; d.colorCursor = w->colorCursor.p; d.li_sorted = w->li_sorted.p; d.li_ref = w->li_ref.p;
-	d.bodyClaim = w->bodyClaim.p; d.bodyColorMask = w->bodyColorMask.p; d.bodyActive = w->bodyActive.p; d.bodyRest = w->bodyRest.p; d.b_posv = w->b_posv.p; d.dfRank = nullptr; d.dfInbox = nullptr; d.evKey = w->evKey.p; d.evInfo = w->evInfo.p; d.eventsOn = w->eventsOn ? 1 : 0; d.uncolList = w->uncolList.p; d.compactList = w->compactList.p; d.hubRowOf = w->hubRowOf.p; d.hubList = w->hubList.p; d.hubDelta = w->hubDelta.p; d.hubMeta = w->hubMeta.p; d.hubFirst = w->hubFirst.p; d.lc = w->lc.p; d.warmDelta = w->warmDelta.p; d.rootPen = w->rootPen.p;
-	d.rootDone = w->rootDone.p; d.rootSleepMin = w->rootSleepMin.p;
-	d.moveBuf = w->moveBuf.p; d.gridCount = w->gridCount.p; d.gridStart = w->gridStart.p; d.gridCursor = w->gridCursor.p;
-	d.gridItems = w->gridItems.p; d.gridFat = w->gridFat.p; d.arriveTree = w->arriveTree.p; d.largeProxies = w->largeProxies.p; d.largeMoves = w->largeMoves.p;
-	d.pairKey = w->pairKey.p; d.pairProxy = w->pairProxy.p; d.pairKey2 = w->pairKey2.p; d.pairProxy2 = w->pairProxy2.p;
-	d.pairFirst = w->pairFirst.p; d.pairRank = w->pairRank.p;
-	d.scanTmp = w->scanTmp.p; d.radixHist = w->radixHist.p; d.keepFlag = w->keepFlag.p; d.keepScan = w->keepScan.p;
-	d.stateOut = w->stateOut.p;
-	d.b_proxyHead = w->b_proxyHead.p; d.p_next = w->p_next.p; d.toiList = w->toiList.p;
-	d.toiPos2c = w->toiPos2c.p; d.toiDestroyList = w->toiDestroyList.p; d.toiNewList = w->toiNewList.p;
-	d.b_toiGroup = w->b_toiGroup.p; d.toiGroups = w->toiGroups.p; d.toiGroupCount = w->toiGroupCount.p; d.toiGroupList = w->toiGroupList.p; d.toiMoved = w->toiMoved.p; d.toiNew = w->toiNew.p; d.toiParent = w->toiParent.p; d.toiDomOf = w->toiDomOf.p; d.toiDomRoot = w->toiDomRoot.p; d.toiDomCount = w->toiDomCount.p; d.toiDomBase = w->toiDomBase.p; d.toiDomFill = w->toiDomFill.p; d.toiDomFailed = w->toiDomFailed.p; d.toiDomEvents = w->toiDomEvents.p; d.toiDomList = w->toiDomList.p; d.toiHull = w->toiHull.p;
-	d.snapBody = w->snapBody.p; d.snapFat = w->snapFat.p;
-	d.b_blk1 = w->b_blk1.p; d.b_adopt = w->b_adopt.p; d.b_adoptStage = w->b_adoptStage.p; d.blkRows = w->blkRows.p; d.blkRowStart = w->blkRowStart.p; d.blkCursor = w->blkCursor.p; d.blkBodyCount = w->blkBodyCount.p; d.blkBodyCursor = w->blkBodyCursor.p;
-	d.blkBodyStart = w->blkBodyStart.p; d.blkBodies = w->blkBodies.p; d.rowColor = w->rowColor.p; d.b_cutv = w->b_cutv.p;
-	d.spatial = w->spatial ? 1 : 0; d.b_owner = w->b_owner.p; d.spNewOwner = w->spNewOwner.p; d.spAwake = w->spAwake.p; d.spFullRows = w->spFullRows ? 1 : 0; d.spStraddle = w->spStraddle.p;
-	d.capStraddle = (int)w->spStraddle.cap; d.spCount = w->spCount.p; d.spTarget = w->spTarget.p; d.spTailKey = w->spTailKey.p;
+	d.gridMask = (uint32_t)(z.gridSize - 1);
+	d.dfRank = nullptr; d.dfInbox = nullptr; d.eventsOn = w->eventsOn ? 1 : 0;
+	d.spatial = w->spatial ? 1 : 0; d.spFullRows = w->spFullRows ? 1 : 0; d.capStraddle = (int)w->spStraddle.cap;
 	if (w->spatial && w->spOwnCapRows < nb)
 	{
-		if (w->spOwnHost) { HIP_TRY(hipStreamSynchronize(s)); (void)hipHostFree(w->spOwnHost); }
-		w->spOwnHost = nullptr;
+		if (w->spOwnHost) HIP_TRY(hipStreamSynchronize(s));
+		w->spOwnHost.free();
 		w->spOwnCapRows = 2 * nb;
-		HIP_TRY(hipHostMalloc((void**)&w->spOwnHost, w->spOwnCapRows * 11 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-		HIP_TRY(hipHostGetDevicePointer((void**)&w->spOwnDev, w->spOwnHost, 0));
+		rc = w->spOwnHost.alloc(w->spOwnCapRows * 11, hipHostMallocMapped | hipHostMallocCoherent);
+		if (rc) return rc;
 	}
-	d.spOwnOut = w->spatial ? w->spOwnDev : nullptr; d.spOwnCap = (int)w->spOwnCapRows;
+	d.spOwnOut = w->spatial ? w->spOwnHost.dev : nullptr; d.spOwnCap = (int)w->spOwnCapRows;
 	d.userFilter = hasFilter(w) ? 1 : 0; d.preSolveOn = hasPreSolve(w) ? 1 : 0; d.postSolveOn = w->postSolveOn ? 1 : 0;
-	d.pre_o0 = w->pre_o0.p; d.pre_o1 = w->pre_o1.p; d.pre_oimp = w->pre_oimp.p; d.pre_o3 = w->pre_o3.p;
-	d.preRecs = w->preRecs.p; d.postRecs = w->postRecs.p; d.filterList = w->filterList.p;
 	d.toiLog = listenerOn(w) && w->def.continuous ? w->toiLog.p : nullptr;
 	d.capToiLog = (int)std::min<size_t>(w->toiLog.cap, 0x7fffff);
 	d.toiVerdict = hasPreSolve(w) && w->def.continuous ? w->toiVerdict.p : nullptr;

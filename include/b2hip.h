@@ -692,6 +692,10 @@ int b2hip_test_radix_sort(b2hip_world* w, int count, uint64_t* keys, int* payloa
  * not hold, [2] live entries minus live contacts (entries of dead contacts that survived), [3] recounted minus tracked
  * fill, [4] live entries, [5] tombstones. A kept set is right when [1] = [2] = [3] = 0. */
 int b2hip_test_keyset_check(b2hip_world* w, long long out[6]);
+/* Test hook: the world's storage. out[0] blocks of device and pinned host memory the library's owner types hold in this
+ * process right now, all worlds together (w may be null): back at its earlier value once a world is destroyed. out[1] device
+ * arrays of `w` whose pointer in the kernels' argument block is not the array's current one (0 for a null world): always 0. */
+int b2hip_test_storage(b2hip_world* w, long long out[2]);
 
 /* World snapshot (checkpoint / resume; the reference only has the lossy text b2World::Dump, b2World.cpp:2107-2164).
  * Everything that survives a step: bodies, shapes, fixtures with their proxy ids and fat AABBs, joints with their
