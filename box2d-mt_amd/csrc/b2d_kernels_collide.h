@@ -257,6 +257,10 @@ __device__ __forceinline__ bool b2dSameBits4(float4 a, float4 b)
 struct DW;
 __device__ __forceinline__ bool keysetMaintained(const DW& W);
 __device__ __forceinline__ bool htDelete(const DW& W, uint32_t mask, uint64_t key);
+// (the island build's union pass and the colour check's voiding as the UNION form runs them: b2d_kernels_island.h, b2d_kernels_solve_large.h)
+__device__ __forceinline__ bool contactSolid(uint32_t flags);
+__device__ __forceinline__ void collideUnionTail(const DW& W, bool solid, int newIndex, int bodyA, int bodyB);
+__device__ __forceinline__ int collideVoidColor(const DW& W, uint32_t flags, int color);
 
 // What the COMPACT form of the narrow phase is handed beside the world (b2hip_host_phases.h: phaseCollide).
 struct CollideCompactArgs
@@ -309,7 +313,9 @@ __attribute__((amdgpu_waves_per_eu((!ORDER && !STAGE) ? 4 : 1, (!ORDER && !STAGE
 k_collide(DW W, int sortTile)
 {
 	constexpr bool COMPACT = false;
+	constexpr bool UNION = false;
 	const CollideCompactArgs cc = CollideCompactArgs();
+	const int voidColors = 0;
 #include "b2d_kernels_collide_body.h"
 }
 
@@ -323,6 +329,24 @@ __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_collide(DW W, int sortTile, CollideCompactArgs cc)
 {
 	static_assert(STAGE == 0 && !ORDER && COMPACT, "the form that stores the compacted array: k_collide<0, false, true>");
+	constexpr bool UNION = false;
+	const int voidColors = 0;
+#include "b2d_kernels_collide_body.h"
+}
+
+// UNION: the COMPACT form with the island build's union pass as its tail. A lane that stores a surviving contact holds its
+// ids, its new flags and its new index: what k_island_union reads again for the one contact in seven that is solid. Behind
+// the stores of its chunk a workgroup counts the degrees, hands out the places in the adjacency segments and unites the
+// bodies of its solid survivors (collideUnionTail, b2d_kernels_island.h), and stores every survivor without CF_ISLAND and -
+// `voidColors`: the island build will run k_color_check - with the colour that kernel's first loop would leave it
+// (collideVoidColor, b2d_kernels_solve_large.h). The forest is seeded in front of this launch (k_union_seed); the island
+// build then starts at k_island_flatten (b2hip_host_phases.h: phaseCollide, buildIslands).
+template <int STAGE, bool ORDER, bool COMPACT, bool UNION>
+__global__ __launch_bounds__(256) void
+__attribute__((amdgpu_waves_per_eu(4, 4)))
+k_collide(DW W, int sortTile, CollideCompactArgs cc, int voidColors)
+{
+	static_assert(STAGE == 0 && !ORDER && COMPACT && UNION, "COMPACT with the union tail: k_collide<0, false, true, true>");
 #include "b2d_kernels_collide_body.h"
 }
 

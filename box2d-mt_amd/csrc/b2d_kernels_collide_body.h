@@ -1,6 +1,7 @@
 // b2d_kernels_collide_body.h - the body of the narrow-phase kernel, included once per form by b2d_kernels_collide.h (no include
-// guard on purpose). In scope where it is included: DW W, int sortTile, CollideCompactArgs cc, and the constants STAGE,
-// ORDER, COMPACT. Text, not a function: the forms that existed before COMPACT compile to the instruction streams they had.
+// guard on purpose). In scope where it is included: DW W, int sortTile, CollideCompactArgs cc, int voidColors, and the constants
+// STAGE, ORDER, COMPACT, UNION (UNION only with COMPACT). Text, not a function: the forms that existed before UNION compile to
+// the instruction streams they had.
 	b2dPhaseStamp(W);
 	DState* S = W.st;
 	const int n = S->c.nContacts;
@@ -414,17 +415,18 @@
 			if (waveLane() == 0) s_before[threadIdx.x >> 6] = before;
 			__syncthreads();
 			const int j = s_before[0] + s_before[1] + s_before[2] + s_before[3] + rank;
-			if (valid && keep && j <= i) // (j <= i always, unless a look-back gave up)
+			const bool stored = valid && keep && j <= i; // (j <= i always, unless a look-back gave up)
+			if (stored)
 			{
 				B.ids[j] = ids;
 				B.key[j] = key;
-				B.flags[j] = flags;
+				B.flags[j] = UNION ? flags & ~CF_ISLAND : flags; // (UNION: b2World::Solve's wipe, b2World.cpp:1191-1194, as k_island_union does it)
 				B.mat[j] = mat;
 				B.man0[j] = now.man0();
 				B.man1[j] = now.man1();
 				B.imp[j] = now.imp();
 				B.man3[j] = now.man3();
-				B.color[j] = color;
+				B.color[j] = (UNION && voidColors) ? collideVoidColor(W, flags, color) : color;
 				B.mgr[j] = mgr;
 				if (mgr >= 0) W.toiPos2c[mgr] = j;
 			}
@@ -435,6 +437,8 @@
 				// set, never seen - is counted in the first word of ARRIVE_COMPACT's tree, idle and zero while this form runs.)
 				if (!htDelete(W, ksMask, key + 1ull)) __hip_atomic_fetch_add(W.arriveTree + (size_t)ARRIVE_COMPACT * TREE_WORDS, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			}
+			// UNION: the solid survivors join the forest under their new index (every lane arrives here: the tail shuffles)
+			if (UNION) collideUnionTail(W, stored && contactSolid(flags), j, bodyA, bodyB);
 			break; // (one chunk per workgroup)
 		}
 	}

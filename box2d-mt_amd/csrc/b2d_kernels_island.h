@@ -187,7 +187,22 @@ __device__ __forceinline__ int effBlk(const DW& W, int body)
 	return nb > 0 ? ownIdBlock(body, nb) : 0;
 }
 
-__global__ __launch_bounds__(256) void k_island_init(DW W)
+// The forest before any union: every body its own root, no contact counted. Part of k_island_init, unless this step's narrow
+// phase unites the contacts itself (k_collide<0, false, true, true>): then this launch goes in front of it.
+__global__ __launch_bounds__(256) void k_union_seed(DW W)
+{
+	b2dPhaseStamp(W);
+	const int n = W.nBodies;
+	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+	{
+		W.parent[i] = i;
+		W.deg[i] = 0;
+	}
+}
+
+// `seeded`: k_union_seed has run in front of this step's narrow phase, which has united the contacts since - parent and deg
+// hold this step's forest and degrees and are left alone.
+__global__ __launch_bounds__(256) void k_island_init(DW W, int seeded)
 {
 	b2dPhaseStamp(W);
 	DState* S = W.st;
@@ -202,13 +217,16 @@ __global__ __launch_bounds__(256) void k_island_init(DW W)
 	const int n = W.nBodies;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
 	{
-		W.parent[i] = i;
+		if (!seeded)
+		{
+			W.parent[i] = i;
+			W.deg[i] = 0;
+		}
 		// (rootSeed / rootBodies start with the body's OWN contribution, below: a body that stays its own root - 97 % of the
 		// bodies of the 1 M field - then sends no atomic at all in k_island_flatten; only members add to their root)
 		W.rootContacts[i] = 0;
 		W.rootJoints[i] = 0;
 		W.rootIsland[i] = ROOT_NONE;
-		W.deg[i] = 0;
 		W.adjCursor[i] = 0;
 		W.b_slot[i] = -1;
 		W.b_island[i] = -1;
@@ -316,6 +334,43 @@ __device__ __forceinline__ int solidTileGather(const ContactArrays& C, int n, in
 	return t->n;
 }
 
+// k_island_union's work for the solid survivors of one wave of the narrow phase's UNION form (b2d_kernels_collide.h), called
+// by every lane behind the stores of its chunk: `solid` lanes hold a contact stored at `newIndex` with contactSolid flags.
+// The wave's solid contacts - nine of 64 in the settled Tumbler - are moved to its first lanes, in contact order: the
+// contacts of one fixture then sit side by side again and share their atomic on the body's degree (waveRunAlloc), and the
+// walks run in as few instructions as k_island_union's list gives them. The move is three wave permutes, not a list in LDS:
+// a list of a chunk's (index, body, body) is 3 KB, the form has 700 bytes to spare before its fourth workgroup per CU is
+// gone, and the workgroup's wave slots are held until its last wave ends whichever lanes walk.
+// Nothing here waits for another workgroup: the degrees are atomics, the unions lock-free (ufUnionFrom), and a body's
+// places in its adjacency segment depend on the order of arrival exactly as they do in k_island_union.
+__device__ __forceinline__ void collideUnionTail(const DW& W, bool solid, int newIndex, int bodyA, int bodyB)
+{
+	const unsigned long long m = __ballot(solid);
+	if (m == 0ull) return; // (the whole wave)
+	const int lane = waveLane(), count = __popcll(m);
+	const int below = __popcll(m & ((1ull << lane) - 1ull));
+	// (a permutation of the lanes: the solid ones to the front, the others behind them - every lane sends, every lane receives)
+	const int dest = (solid ? below : count + (lane - below)) << 2;
+	const int i = __builtin_amdgcn_ds_permute(dest, newIndex);
+	const int ea = __builtin_amdgcn_ds_permute(dest, bodyA);
+	const int eb = __builtin_amdgcn_ds_permute(dest, bodyB);
+	const bool live = lane < count;
+	const int a = live ? ea : 0, b = live ? eb : 0;
+	// (the body flags are fetched again, beside the first level of both walks: carried from the top of the kernel they cost
+	// the evaluation six more spilled registers)
+	const uint32_t bfA = W.b_flags[a], bfB = W.b_flags[b];
+	const bool liveA = live && (bfA & BF_TYPE_MASK) != BT_STATIC, liveB = live && (bfB & BF_TYPE_MASK) != BT_STATIC;
+	const int pa = __hip_atomic_load(&W.parent[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	const int pb = __hip_atomic_load(&W.parent[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	int2 slot = make_int2(-1, -1);
+	const int sa = waveRunAlloc(W.deg, a, liveA), sb = waveRunAlloc(W.deg, b, liveB);
+	if (liveA) slot.x = sa;
+	if (liveB) slot.y = sb;
+	if (liveA && liveB) ufUnionFrom(W.parent, a, b, pa, pb);
+	if (live) W.adjSlot[i] = slot;
+}
+
+// `rounds` 0: the joints only - the contacts were united by this step's narrow phase (collideUnionTail).
 __global__ __launch_bounds__(256) void k_island_union(DW W, int rounds)
 {
 	b2dPhaseStamp(W);
@@ -324,7 +379,7 @@ __global__ __launch_bounds__(256) void k_island_union(DW W, int rounds)
 	const ContactArrays& C = W.ca[S->cur];
 	__shared__ SolidTile s_tile;
 	const int tile = rounds * 256;
-	for (int base = blockIdx.x * tile; base < n; base += gridDim.x * tile)
+	for (int base = blockIdx.x * tile; tile > 0 && base < n; base += gridDim.x * tile)
 	{
 		const int m = solidTileGather<true>(C, n, base, rounds, &s_tile);
 		for (int j0 = 0; j0 < m; j0 += 256)

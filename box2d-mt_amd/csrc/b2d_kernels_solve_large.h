@@ -189,7 +189,17 @@ __global__ __launch_bounds__(256) void k_color_begin(DW W)
 // Colours persist with the contact (ContactArrays::color). A step can reuse them if every constraint of
 // the large islands already has one and no two constraints on a body share a colour; otherwise the host
 // runs the colouring rounds again. Also builds the per-colour census for the reuse case.
-__global__ __launch_bounds__(256) void k_color_check(DW W)
+// The colour loop (1) below leaves a contact of a world WITHOUT a partition, as this step's narrow phase stores it when it
+// takes the UNION form with `voidColors` (b2d_kernels_collide.h) - the same tests on the same flags, loop (1) for loop (1).
+__device__ __forceinline__ int collideVoidColor(const DW& W, uint32_t flags, int color)
+{
+	if (color < 0 || color >= MAX_COLORS || W.st->c.nBlocks != 0) return color; // (with a partition loop (1) runs as ever)
+	if ((flags & (CF_TOUCHING | CF_SENSOR)) != CF_TOUCHING) return -1;
+	return ((1ull << color) & colorStaleMask(false)) ? -1 : color;
+}
+
+// `voided`: this step's narrow phase has done loop (1) for a world without a partition (collideVoidColor).
+__global__ __launch_bounds__(256) void k_color_check(DW W, int voided)
 {
 	b2dPhaseStamp(W);
 	DState* S = W.st;
@@ -213,7 +223,7 @@ __global__ __launch_bounds__(256) void k_color_check(DW W)
 	// (1) every touching contact that owns a colour - large island or not, asleep or not - reserves it on its bodies.
 	// A contact that stopped touching gives its colour back: reservations of idle neighbours (a pyramid box has two of
 	// them) would push new constraints to ever higher colours, and the depth of a sweep is the number of colours.
-	const int nAll = S->c.nContacts;
+	const int nAll = (voided && noPart) ? 0 : S->c.nContacts;
 	for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nAll; i += gridDim.x * blockDim.x)
 	{
 		// (colour and flags together - one round trip, not two in a row, for the one contact in seven of a dense pile that owns

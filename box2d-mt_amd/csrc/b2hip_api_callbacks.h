@@ -216,6 +216,8 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 // 30: two long longs: batched b2hip_fixture_set_sensors / _thicks calls since the world was created [0] whose list of contacts
 //     with a changed TOI candidacy went through the radix sort (the same threshold and hook), [1] that listed a second time
 //     because the first listing's room was short (B2HIP_TEST_FIXTURE_LIST_ROOM lowers that room).
+// 31: one long long: island builds since the world was created that ran no union pass over the contacts, because the step's
+//     narrow phase - k_collide<0, false, true, true> - had united them (B2HIP_COLLIDE_UNION=0: never).
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -278,6 +280,12 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 	{
 		if (first != 0 || count != 1) return setError(B2HIP_ERR_INVALID, "narrow-phase statistics: [0, 1)");
 		memcpy(out, &w->statCollideCompact, sizeof(long long));
+		return 0;
+	}
+	case 31:
+	{
+		if (first != 0 || count != 1) return setError(B2HIP_ERR_INVALID, "island-build statistics: [0, 1)");
+		memcpy(out, &w->statUnionSkipped, sizeof(long long));
 		return 0;
 	}
 	case 29:

@@ -326,6 +326,7 @@ int b2hip_load_snapshot(const void* buffer, size_t size, int device, b2hip_world
 	w->stateCount = h.stateCount;
 	*w->h_dstate = ds;
 	w->contactsKnown = false;
+	forestDrop(w);
 #define SNAP_UP(arr, s) do { if ((s).bytes && hipMemcpy(w->arr.p, (s).p, (s).bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(setError(B2HIP_ERR_HIP, "snapshot upload failed (" #arr ")")); } while (0)
 	if (hipMemcpy(w->d_state.p, &ds, sizeof(DState), hipMemcpyHostToDevice) != hipSuccess) return fail(setError(B2HIP_ERR_HIP, "snapshot upload failed (state block)"));
 	w->pubSeq = ds.pubCount; // (the device numbers its census publications; the host counts along)

@@ -23,6 +23,7 @@ static int stepBeginImpl(b2hip_world* w, float dt, int velocity_iterations, int 
 	}
 	w->stepActive = true;
 	w->stepSolves = w->stepComplete;
+	forestDrop(w);
 	w->dw.toiContinue = w->stepComplete ? 0 : 1;
 	w->dw.toiEventCap = w->def.sub_stepping ? 1 : 0;
 	// k_step_begin zeroes the per-step counters (it keeps nContacts / nMoves / cur)
@@ -263,6 +264,7 @@ int b2hip_find_new_contacts(b2hip_world* w)
 static int solveToiImpl(b2hip_world* w)
 {
 	w->toiStep.begin();
+	forestDrop(w); // (the TOI phase counts degrees of its own in DW::deg and changes contacts)
 	w->dw.nToiVerdict = 0;
 	w->last.nToiList = w->last.nToiCalls = w->last.nToiEvents = 0;
 	if (w->def.continuous && w->sp.dt > 0.0f)

@@ -215,6 +215,7 @@ static int growPairBuffers(b2hip_world* w)
 static int findNewContacts(b2hip_world* w, bool sync)
 {
 	w->contactsKnown = false; // (until the read-back behind it: contacts and TOI candidates are created)
+	forestDrop(w);
 	for (int attempt = 0; sync && attempt < 4; ++attempt)
 	{
 		int rc = findNewContactsOnce(w, true);
@@ -285,6 +286,7 @@ static int phaseCollide(b2hip_world* w)
 	// occupancy gives)
 	const bool split = w->collideSplitEnv < 0 ? w->last.nContacts >= 262144 : w->collideSplitEnv != 0;
 	DW& d = w->dw;
+	forestDrop(w); // (a narrow phase changes the contact array)
 	if (int rk = ktBracket(w, 2, 5)) return rk;
 	// (shape records staged through LDS where the world holds many distinct ones: b2d_kernels_collide.h)
 	// Measured (tools/gpu_collide_variants.py, profiles/r04_collide_variants.txt): on the 1 M-body field (a record per body,
@@ -331,7 +333,18 @@ static int phaseCollide(b2hip_world* w)
 		cc.tag = ++w->collideEpoch;
 		cc.chunk = w->collideChunk;
 		w->statCollideCompact += 1;
-		LAUNCH(w, (k_collide<0, false, true>), (int)std::max<size_t>(chunks, 1), 256, d, uni, cc);
+		// (with the island build's union pass as its tail when an island build follows: b2d_kernels_collide.h. The forest is seeded
+		// by a launch of its own - k_step_begin is one wave, and the pass over the bodies belongs to the steps that take this
+		// form. The colours are voided there too when the island build will run k_color_check: buildIslands, s.largeHint.)
+		if (w->collideUnionOn && w->sp.dt > 0.0f && w->stepSolves)
+		{
+			const bool voidColors = w->largeHintSteps > 0;
+			LAUNCH(w, k_union_seed, gridFor(d.nBodies), 256, d);
+			LAUNCH(w, (k_collide<0, false, true, true>), (int)std::max<size_t>(chunks, 1), 256, d, uni, cc, voidColors ? 1 : 0);
+			w->forestUnited = true;
+			w->forestVoided = voidColors;
+		}
+		else LAUNCH(w, (k_collide<0, false, true>), (int)std::max<size_t>(chunks, 1), 256, d, uni, cc);
 		return ktBracket(w, 2, 5);
 	}
 	if (stage) LAUNCH(w, (k_collide<1, true>), gridFor(d.capContacts), 256, d, sort);
@@ -382,7 +395,7 @@ static int partitionLargeIslands(b2hip_world* w, int targetDeg)
 	deviceExclusiveScan<int>(w->stream, d.pairFirst, d.pairRank, d.scanTmp, w->scanCtx, nPtr, d.nBodies);
 	LAUNCH(w, k_part_assign, gridFor(d.nBodies), 256, d, vin, d.pairRank);
 	LAUNCH(w, k_color_recheck_begin, gridFor(d.nBodies), 256, d);
-	LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
+	LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d, 0);
 	LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
 	LAUNCH(w, k_block_census, 1, 1024, d, (DState*)nullptr);
 	return 0;
@@ -427,8 +440,16 @@ static int buildIslands(b2hip_world* w, const SolveStep& s)
 	while (solidRounds < SOLID_TILE_ROUNDS_MAX && (long long)w->last.nContacts >= 2ll * solidRounds * 256 * 1024) solidRounds *= 2;
 	if (w->solidRoundsEnv > 0) solidRounds = w->solidRoundsEnv;
 	const int gSolid = gridFor((size_t)(d.capContacts + solidRounds - 1) / solidRounds);
-	LAUNCH(w, k_island_init, gridFor(d.nBodies), 256, d);
-	LAUNCH(w, k_island_union, gSolid, 256, d, solidRounds);
+	// (the contacts united by this step's narrow phase: the joints only, and k_color_check without its first loop)
+	const bool united = w->forestUnited, voided = united && w->forestVoided && s.largeHint;
+	forestDrop(w);
+	LAUNCH(w, k_island_init, gridFor(d.nBodies), 256, d, united ? 1 : 0);
+	if (!united) LAUNCH(w, k_island_union, gSolid, 256, d, solidRounds);
+	else
+	{
+		w->statUnionSkipped += 1;
+		if (d.nJoints > 0) LAUNCH(w, k_island_union, gridFor(d.nJoints), 256, d, 0);
+	}
 	LAUNCH(w, k_island_flatten, gridFor(d.nBodies), 256, d);
 	LAUNCH(w, k_island_count, gSolid, 256, d, solidRounds);
 	LAUNCH(w, k_island_classify, gridFor(d.nBodies), 256, d, w->forceLarge, w->sp);
@@ -446,7 +467,7 @@ static int buildIslands(b2hip_world* w, const SolveStep& s)
 	// (colour bookkeeping and block census only matter to large islands: skipped while the world has had none lately)
 	if (s.largeHint)
 	{
-		LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
+		LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d, voided ? 1 : 0);
 		LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
 		LAUNCH(w, k_block_census, 1, 1024, d, pubBy == 1 ? w->h_pub.dev : (DState*)nullptr);
 	}
@@ -490,7 +511,7 @@ static int recheckColors(b2hip_world* w, SolveStep& s)
 {
 	DW& d = w->dw;
 	LAUNCH(w, k_color_recheck_begin, gridFor(d.nBodies), 256, d);
-	LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
+	LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d, 0);
 	LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
 	LAUNCH(w, k_block_census, 1, 1024, d, (DState*)nullptr);
 	if (int rc = readState(w)) return rc;
@@ -510,7 +531,7 @@ static int largeIslandPolicy(b2hip_world* w, SolveStep& s)
 		if (!s.largeHint)
 		{
 			// the first large island after a while: run what was skipped, look again
-			LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d);
+			LAUNCH(w, k_color_check, gridFor(d.capContacts), 256, d, 0);
 			LAUNCH(w, k_color_masks, gridFor(d.nBodies), 256, d);
 			LAUNCH(w, k_block_census, 1, 1024, d, (DState*)nullptr);
 			if (int rc = readState(w)) return rc;

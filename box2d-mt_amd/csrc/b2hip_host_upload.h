@@ -336,6 +336,7 @@ static int uploadScanLengths(b2hip_world* w)
 // Upload bodies / fixtures / shapes / joints created or edited since the last step: the stages above, in this order.
 static int flushEdits(b2hip_world* w)
 {
+	forestDrop(w); // (bodies, fixtures and joints may change under the forest)
 	int rc = ensureCapacity(w, (size_t)w->lastContacts);
 	if (!rc) rc = uploadDirtyBodies(w);
 	if (!rc) rc = uploadSeedOrder(w);
@@ -414,6 +415,7 @@ static int editOpsTail(b2hip_world* w, bool destroys, bool betweenSteps)
 
 static int applyEditOps(b2hip_world* w, bool betweenSteps)
 {
+	forestDrop(w); // (destroyed contacts leave the array)
 	if (w->editOps.empty()) return 0;
 	bool destroys = false;
 	for (size_t k = 0; k < w->editOps.size(); ++k) destroys = destroys || w->editOps[k].x == EDIT_DESTROY_BODY || w->editOps[k].x == EDIT_DESTROY_FIXTURE;

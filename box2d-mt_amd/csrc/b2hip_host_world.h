@@ -563,6 +563,11 @@ struct b2hip_world
 	bool contactsKnown = false;    // h_dstate holds the contact count and the TOI slot count as they are on the device: true behind a step's last read-back and behind applyEditOps', false once a narrow phase or a pair update is queued
 	unsigned collideEpoch = 0;     // tag of its last launch (16 bits, never 0; the status words: collideCounts, collideGroups)
 	long long statCollideCompact = 0; // narrow phases that took that form since the world was created (b2hip_debug_read 24)
+	// k_collide<0, false, true, true>: that form with the island build's union pass as its tail (b2d_kernels_collide.h, b2d_kernels_island.h)
+	bool collideUnionOn = true;    // B2HIP_COLLIDE_UNION=0: never (k_island_union in every island build)
+	bool forestUnited = false;     // this step's narrow phase seeded the forest and united the contacts, and nothing has been queued since that changes the contact array or the forest: set by phaseCollide, consumed by buildIslands, dropped by forestDrop()
+	bool forestVoided = false;     // ... and stored the colours as k_color_check's first loop leaves them
+	long long statUnionSkipped = 0; // island builds that ran no union pass over the contacts since the world was created (b2hip_debug_read 31)
 	bool collideUniOff = false;  // B2HIP_COLLIDE_UNI=0: k_collide reads every shape record from memory (no staged pair of records)
 	int collideSortEnv = -1;     // B2HIP_COLLIDE_SORT=0 / 1: k_collide never / always sorts the contacts of a tile by shape-pair class in LDS
 	hipStream_t stream2 = nullptr; // small-island solver beside the large-island one
@@ -1071,6 +1076,15 @@ static int ktRecord(b2hip_world* w)
 	return 0;
 }
 
+// The record that this step's narrow phase united the contacts (b2hip_world::forestUnited) is dropped by whatever queues a
+// narrow phase, a pair update, a compaction or any other change of the contact array or of parent / deg behind it - and by
+// the start of a step: an island build never finds a forest that is not its own contacts'.
+static void forestDrop(b2hip_world* w)
+{
+	w->forestUnited = false;
+	w->forestVoided = false;
+}
+
 // b2hip_set_kernel_timing modes 2 / 3 / 4: an event pair around k_collide / k_sync_fixtures / k_find_pairs_small
 static int ktBracket(b2hip_world* w, int mode, int kind)
 {
@@ -1168,6 +1182,7 @@ static void readSwitches(b2hip_world* w)
 	if (const char* e = getenv("B2HIP_SOLID_ROUNDS")) { const int v = atoi(e); w->solidRoundsEnv = (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0; }
 	w->collideSplitEnv = envInt("B2HIP_COLLIDE_SPLIT", -1);
 	w->collideCompactOn = envInt("B2HIP_COLLIDE_COMPACT", 1) != 0;
+	w->collideUnionOn = envInt("B2HIP_COLLIDE_UNION", 1) != 0;
 	w->collideChunk = std::min(std::max(envInt("B2HIP_TEST_COLLIDE_CHUNK", 256), 1), 256);
 	w->lifecycleSortMax = std::min(std::max(envInt("B2HIP_TEST_LIFECYCLE_SORT_MAX", LIFECYCLE_SORT_MAX), 0), LIFECYCLE_SORT_MAX);
 	w->fixtureListRoom = std::max(envInt("B2HIP_TEST_FIXTURE_LIST_ROOM", -1), -1);
