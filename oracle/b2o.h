@@ -110,6 +110,27 @@ void b2o_get_joint_reaction(const b2o_world* w, int joint, float inv_dt, float o
 void b2o_apply_force(b2o_world* w, int body, float fx, float fy, float torque, int wake);
 void b2o_set_velocity(b2o_world* w, int body, float vx, float vy, float omega);
 void b2o_step(b2o_world* w, float dt, int velocity_iterations, int position_iterations);
+/* The visiting order of the NEXT island solve (b2o_step / b2o_phase_solve), used once and cleared behind it: the oracle as
+ * the sequential sweep in the order of the device's large-island plan (tests/solve_order_ref.py, tests/test_gpu_solve_replay.py).
+ *   entries       one per contact of a large island, named as both sides report it (the fixture ids of b2o_get_contacts /
+ *                 b2hip_get_contacts: a chain's child edge is a fixture of its own at this level), with its rank
+ *   body_large    one byte per body: in a large island this step
+ * An island whose non-static bodies all carry the flag has its contacts visited in ascending rank - stable: ties keep the
+ * reference's order, they are independent rows - in InitVelocityConstraints / WarmStart, every velocity iteration,
+ * StoreImpulses and every position iteration; with joints_by_id != 0 its joints are walked in ascending joint id (before the
+ * contacts in a velocity iteration, behind them in a position iteration: b2Island::Solve). Everything else - the island build,
+ * integration, the per-island position early-out, sleeping, the islands without the flag - is the reference's.
+ * It does not guess: errors[0] counts contacts of a flagged island that have no rank, errors[1] ranked contacts no flagged
+ * island took plus islands whose non-static bodies are only partly flagged (such an island keeps the reference's order). */
+typedef struct b2o_order_entry { int32_t fixture_a, fixture_b, rank; } b2o_order_entry;
+void b2o_set_solve_order(b2o_world* w, int count, const b2o_order_entry* entries, int body_count, const unsigned char* body_large,
+	int joints_by_id);
+/* the two counts of the last solve that used an order (zeroed by b2o_set_solve_order) */
+void b2o_get_solve_order_errors(const b2o_world* w, int32_t errors[2]);
+/* the order the last island solve visited its contacts in, island after island (rank = place in its island, 0 where the next
+ * island begins): the reference's own order where no order was set. Returns the number of records (may exceed cap). */
+void b2o_record_solve_order(b2o_world* w, int enable);
+int b2o_get_recorded_solve_order(const b2o_world* w, int cap, b2o_order_entry* out);
 int b2o_body_count(const b2o_world* w);
 /* 10 floats per body: px, py, angle, vx, vy, w, cx, cy, flags(bits), sleepTime  (== b2hip_body_state) */
 void b2o_get_body_states(const b2o_world* w, float* out10);

@@ -397,6 +397,24 @@ int b2hip_get_fat_aabbs(b2hip_world* w, int first, int count, float* out4n)
 	return 0;
 }
 
+/* the oracle's solve order hook (b2o.h) on a world of this shim: what tests/test_gpu_solve_replay.py drives. No such entry
+ * exists in the product. */
+int b2o_shim_set_solve_order(b2hip_world* w, int count, const b2o_order_entry* entries, int body_count, const unsigned char* body_large,
+	int joints_by_id)
+{
+	b2o_set_solve_order(w->o, count, entries, body_count, body_large, joints_by_id);
+	return 0;
+}
+
+int b2o_shim_get_solve_order_errors(b2hip_world* w, int32_t errors[2])
+{
+	b2o_get_solve_order_errors(w->o, errors);
+	return 0;
+}
+
+int b2o_shim_record_solve_order(b2hip_world* w, int enable) { b2o_record_solve_order(w->o, enable); return 0; }
+int b2o_shim_get_recorded_solve_order(b2hip_world* w, int cap, b2o_order_entry* out) { return b2o_get_recorded_solve_order(w->o, cap, out); }
+
 int b2hip_get_profile(b2hip_world* w, float ms[13])
 {
 	(void)w;

@@ -159,6 +159,15 @@ struct b2o_world
 	int postSolveOn;
 	b2o_contact_impulse* postSolve; int nPostSolve, capPostSolve;
 	int* postSolveSlot; int capPostSolveSlot; /* contact slot of each record until the end of the step */
+	/* the visiting order of the next island solve (b2o_set_solve_order): used once, cleared behind it */
+	int orderOn, orderJointsById;
+	b2o_order_entry* order; int nOrder;      /* sorted by (fixture_a, fixture_b) */
+	unsigned char* orderUsed;                /* per entry: a flagged island took it */
+	unsigned char* orderLarge; int nOrderLarge; /* per body: in a large island this step */
+	int32_t orderErrors[2];
+	/* the order the last island solve visited its contacts in (b2o_record_solve_order) */
+	int orderRecord;
+	b2o_order_entry* orderLog; int nOrderLog, capOrderLog;
 };
 
 #define GROW(ptr, cap, need, type)                                            \
@@ -208,6 +217,10 @@ void b2o_world_destroy(b2o_world* w)
 	free(w->bodyOwned);
 	free(w->contactOwned);
 	free(w->jointOwned);
+	free(w->order);
+	free(w->orderUsed);
+	free(w->orderLarge);
+	free(w->orderLog);
 	free(w);
 }
 
@@ -1755,9 +1768,128 @@ static void ex_reorder(b2o_world* w, int* ic, int n, int mode, int D)
 }
 #endif
 
+/* ---- the solve order hook (b2o.h: b2o_set_solve_order) ---------------------------------------------------------------------
+ * The device's coloured large-island solvers are a sequential Gauss-Seidel sweep in the order of their plan (two rows of one
+ * colour share no moving body); with that order handed in, this file's arithmetic must give the device's bits. */
+static int order_key_cmp(const void* a, const void* b)
+{
+	const b2o_order_entry* p = (const b2o_order_entry*)a;
+	const b2o_order_entry* q = (const b2o_order_entry*)b;
+	if (p->fixture_a != q->fixture_a) return p->fixture_a < q->fixture_a ? -1 : 1;
+	if (p->fixture_b != q->fixture_b) return p->fixture_b < q->fixture_b ? -1 : 1;
+	return 0;
+}
+
+void b2o_set_solve_order(b2o_world* w, int count, const b2o_order_entry* entries, int bodyCount, const unsigned char* bodyLarge,
+	int jointsById)
+{
+	free(w->order); free(w->orderUsed); free(w->orderLarge);
+	w->order = (b2o_order_entry*)malloc(sizeof(b2o_order_entry) * (size_t)(count + 1));
+	w->orderUsed = (unsigned char*)calloc((size_t)count + 1, 1);
+	w->orderLarge = (unsigned char*)calloc((size_t)bodyCount + 1, 1);
+	if (count > 0) memcpy(w->order, entries, sizeof(b2o_order_entry) * (size_t)count);
+	if (bodyCount > 0) memcpy(w->orderLarge, bodyLarge, (size_t)bodyCount);
+	qsort(w->order, (size_t)count, sizeof(b2o_order_entry), order_key_cmp);
+	w->nOrder = count;
+	w->nOrderLarge = bodyCount;
+	w->orderJointsById = jointsById != 0;
+	w->orderErrors[0] = w->orderErrors[1] = 0;
+	w->orderOn = 1;
+}
+
+void b2o_get_solve_order_errors(const b2o_world* w, int32_t errors[2])
+{
+	errors[0] = w->orderErrors[0];
+	errors[1] = w->orderErrors[1];
+}
+
+typedef struct { int rank, place, slot; } order_row;
+static int order_row_cmp(const void* a, const void* b)
+{
+	const order_row* p = (const order_row*)a;
+	const order_row* q = (const order_row*)b;
+	if (p->rank != q->rank) return p->rank < q->rank ? -1 : 1;
+	return p->place - q->place; /* stable: ties in the reference's order */
+}
+static int int_cmp(const void* a, const void* b) { return *(const int*)a - *(const int*)b; }
+
+/* called with the island as the DFS found it, just before it is solved */
+static void order_island(b2o_world* w, const int* islandBodies, int bodyCount, int* islandContacts, int contactCount,
+	int* islandJoints, int jointCount)
+{
+	int moving = 0, flagged = 0;
+	for (int i = 0; i < bodyCount; ++i)
+	{
+		const int bi = islandBodies[i];
+		if (w->bodies[bi].type == 0) continue;
+		++moving;
+		flagged += bi < w->nOrderLarge && w->orderLarge[bi];
+	}
+	if (flagged == 0) return;
+	if (flagged != moving)
+	{
+		w->orderErrors[1]++;
+		return;
+	}
+	order_row* rows = (order_row*)malloc(sizeof(order_row) * (size_t)(contactCount + 1));
+	for (int i = 0; i < contactCount; ++i)
+	{
+		const contact_t* c = &w->contacts[islandContacts[i]];
+		b2o_order_entry key;
+		key.fixture_a = c->fixtureA; key.fixture_b = c->fixtureB; key.rank = 0;
+		const b2o_order_entry* e = (const b2o_order_entry*)bsearch(&key, w->order, (size_t)w->nOrder, sizeof(b2o_order_entry), order_key_cmp);
+		rows[i].place = i;
+		rows[i].slot = islandContacts[i];
+		if (e && !w->orderUsed[e - w->order])
+		{
+			rows[i].rank = e->rank;
+			w->orderUsed[e - w->order] = 1;
+		}
+		else
+		{
+			rows[i].rank = 0x7fffffff;
+			w->orderErrors[0]++;
+		}
+	}
+	qsort(rows, (size_t)contactCount, sizeof(order_row), order_row_cmp);
+	for (int i = 0; i < contactCount; ++i) islandContacts[i] = rows[i].slot;
+	free(rows);
+	if (w->orderJointsById) qsort(islandJoints, (size_t)jointCount, sizeof(int), int_cmp);
+}
+
+void b2o_record_solve_order(b2o_world* w, int enable) { w->orderRecord = enable != 0; w->nOrderLog = 0; }
+int b2o_get_recorded_solve_order(const b2o_world* w, int cap, b2o_order_entry* out)
+{
+	for (int i = 0; i < w->nOrderLog && i < cap; ++i) out[i] = w->orderLog[i];
+	return w->nOrderLog;
+}
+
+static void order_record(b2o_world* w, const int* islandContacts, int contactCount)
+{
+	GROW(w->orderLog, w->capOrderLog, w->nOrderLog + contactCount + 1, b2o_order_entry);
+	for (int i = 0; i < contactCount; ++i)
+	{
+		b2o_order_entry* e = &w->orderLog[w->nOrderLog++];
+		e->fixture_a = w->contacts[islandContacts[i]].fixtureA;
+		e->fixture_b = w->contacts[islandContacts[i]].fixtureB;
+		e->rank = i;
+	}
+}
+
+static void order_done(b2o_world* w)
+{
+	for (int i = 0; i < w->nOrder; ++i) if (!w->orderUsed[i]) w->orderErrors[1]++;
+	free(w->order); free(w->orderUsed); free(w->orderLarge);
+	w->order = NULL; w->orderUsed = NULL; w->orderLarge = NULL;
+	w->nOrder = w->nOrderLarge = 0;
+	w->orderOn = 0;
+}
+
 static void solve_island(b2o_world* w, int* islandBodies, int bodyCount, int* islandContacts, int contactCount,
 	int* islandJoints, int jointCount, float h, float dtRatio, int velIters, int posIters)
 {
+	if (w->orderOn) order_island(w, islandBodies, bodyCount, islandContacts, contactCount, islandJoints, jointCount);
+	if (w->orderRecord) order_record(w, islandContacts, contactCount);
 	pos_t* positions = (pos_t*)malloc(sizeof(pos_t) * (size_t)(bodyCount + 1));
 	vel_t* velocities = (vel_t*)malloc(sizeof(vel_t) * (size_t)(bodyCount + 1));
 	constraint_t* cs = (constraint_t*)malloc(sizeof(constraint_t) * (size_t)(contactCount + 1));
@@ -2083,6 +2215,7 @@ static void solve_islands(b2o_world* w, float h, float dtRatio, int velIters, in
 	int* islandJoints = (int*)malloc(sizeof(int) * (size_t)(w->nJoints + 1));
 	for (int i = 0; i < nb; ++i) w->bodies[i].label = -1;
 	for (int i = 0; i < w->nJoints; ++i) w->joints[i].islandFlag = 0;
+	w->nOrderLog = 0;
 	for (int seedSlot = 0; seedSlot < w->nNonStatic; ++seedSlot)
 	{
 		/* seeds in m_nonStaticBodies order (b2World.cpp:1207-1221) */
@@ -2201,6 +2334,7 @@ static void solve_islands(b2o_world* w, float h, float dtRatio, int velIters, in
 			free(p->bodies); free(p->contacts); free(p->joints);
 		}
 	}
+	if (w->orderOn) order_done(w);
 	free(pending);
 	free(islandBodies);
 	free(islandContacts);

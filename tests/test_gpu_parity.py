@@ -11,7 +11,9 @@ Bars (written here, stated in DESIGN.md):
   * floats, larger islands solved in coloured order (a different Gauss-Seidel order than the reference's DFS order):
     the bounds measured after ONE step from identical inputs at full config-2 size (tests/test_gpu_onestep.py), the
     looser trajectory tolerance below on a stated horizon, and bit-identity between the solvers that share the colouring
-    (k_solve_blocks, k_blocks_sweep, launch per colour, the three round-1 solvers of the test build).
+    (k_solve_blocks, k_blocks_sweep, launch per colour, the three round-1 solvers of the test build). That the solvers
+    EXECUTE the plan they share - bit-identity to the sequential sweep in plan order, the oracle replaying the device's
+    colours and hub list step by step - is held by tests/test_gpu_solve_replay.py.
 """
 import os
 
