@@ -38,6 +38,7 @@
 #include "b2d_kernels_joint_batch.h"
 #include "b2d_kernels_body_lifecycle.h"
 #include "b2d_kernels_fixture_batch.h"
+#include "b2d_kernels_body_props.h"
 #include "b2d_scan.h"
 #include "b2d_shape_geom.h"
 
@@ -65,4 +66,5 @@ extern "C"
 #include "b2hip_api_joint_batch.h"
 #include "b2hip_api_body_lifecycle.h"
 #include "b2hip_api_fixture_batch.h"
+#include "b2hip_api_body_props.h"
 } // extern "C"

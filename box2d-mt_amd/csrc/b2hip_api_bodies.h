@@ -118,27 +118,8 @@ int b2hip_set_mass_data(b2hip_world* w, int body, const b2hip_mass_data* md)
 		return B2HIP_OK;
 	}
 	if (b.type != B2HIP_DYNAMIC_BODY) return B2HIP_OK;
-	b.invMass = 0.0f;
-	b.I = 0.0f;
-	b.invI = 0.0f;
-	b.mass = md->mass;
-	if (b.mass <= 0.0f) b.mass = 1.0f;
-	b.invMass = 1.0f / b.mass;
-	const V2 center = v2(md->local_center[0], md->local_center[1]);
-	if (md->inertia > 0.0f && (b.flags & BF_FIXEDROT) == 0)
-	{
-		b.I = md->inertia - b.mass * b2dDot(center, center);
-		b.invI = 1.0f / b.I;
-	}
-	const V2 oldCenter = v2(b.cx, b.cy);
-	b.lcx = center.x;
-	b.lcy = center.y;
-	const V2 c = b2dMulXV(hostXf(b), center);
-	b.c0x = b.cx = c.x;
-	b.c0y = b.cy = c.y;
-	const V2 dv = b2dCrossSV(b.w, c - oldCenter);
-	b.vx += dv.x;
-	b.vy += dv.y;
+	storeMass(b, massFromData(b, md));
+	moveCenter(b);
 	b.resetSweep = 1;
 	return B2HIP_OK;
 }

@@ -46,6 +46,43 @@ static int lifecycleTail(b2hip_world* w, int eventsBefore)
 	return lifecycleCarryEvents(w, eventsBefore);
 }
 
+// The contact half of a batch, behind the kernel that has named its bodies in lcNamed (entry + 1): every contact of a named body
+// is destroyed in one grid-wide pass, the names are taken back, the slots of the TOI partition are given back in the loop's
+// order, and the tail of applyEditOps follows. nToi, nContacts, eventsBefore: the counters as lifecycleBegin read them.
+// (b2hip_set_types, b2hip_api_body_props.h, ends here too.)
+static int lifecycleContacts(b2hip_world* w, int n, int nToi, int nContacts, int eventsBefore)
+{
+	hipStream_t s = w->stream;
+	DW& d = w->dw;
+	int rc = 0;
+	HIP_TRY(hipMemsetAsync(w->lcWords.p, 0, sizeof(int), s));
+	// (the list's room is the pair update's key buffer, free between steps: lifecycleBegin has made it hold nToi keys)
+	LAUNCH(w, k_destroy_contacts_of_set, gridFor((size_t)std::max(nContacts, 1)), 256, d, (const int*)w->lcNamed.p, (unsigned long long*)d.pairKey, nToi, w->lcWords.p);
+	LAUNCH(w, k_lifecycle_unname, gridFor((size_t)n), 256, (const int*)w->bcIds.p, n, d.nBodies, w->lcNamed.p);
+	if (nToi > 0) // (a world without TOI candidates pays nothing here)
+	{
+		int listed = 0;
+		HIP_TRY(hipMemcpyAsync(&listed, w->lcWords.p, sizeof(int), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (listed < 0 || listed > nToi) return setError(B2HIP_ERR_HIP, "the batch listed more contacts with a TOI slot than the partition holds");
+		w->statLifecycleLongSorts += listed > w->lifecycleSortMax ? 1 : 0;
+		if (listed > 0 && listed <= w->lifecycleSortMax)
+			LAUNCH(w, k_lifecycle_toi_sort_replay, 1, 1024, d, (unsigned long long*)d.pairKey, (const int*)w->lcWords.p);
+		else if (listed > 0)
+		{
+			// (r ascending, then nContacts - 1 - i ascending: the low word first, LSD)
+			std::vector<std::pair<int, int>> passes;
+			radixPasses(0, radixBits(std::max(nContacts, 1)), passes);
+			radixPasses(32, radixBits(n), passes);
+			uint64_t *kin = d.pairKey, *kout = d.pairKey2;
+			int2 *vin = d.pairProxy, *vout = d.pairProxy2; // (payloads nobody reads)
+			if ((rc = radixSort(w, kin, kout, vin, vout, w->lcWords.p, listed / RADIX_TILE + 1, passes))) return rc;
+			LAUNCH(w, k_lifecycle_toi_replay, 1, 64, d, (const unsigned long long*)kin, (const int*)w->lcWords.p, nToi);
+		}
+	}
+	return lifecycleTail(w, eventsBefore);
+}
+
 // The device side of a batch whose host bookkeeping is done: `ops` one LIFECYCLE_* per entry, `recs` the fixture records.
 // contacts: some entry destroys or deactivates (the contact pass and the tail run, as a queued EDIT_DESTROY_BODY makes
 // applyEditOps run them whether or not a contact goes).
@@ -73,32 +110,7 @@ static int lifecycleDevice(b2hip_world* w, int n, const int32_t* bodies, const s
 		HIP_TRY(hipStreamSynchronize(s)); // (the pinned buffer is the next call's)
 		return B2HIP_OK;
 	}
-	HIP_TRY(hipMemsetAsync(w->lcWords.p, 0, sizeof(int), s));
-	// (the list's room is the pair update's key buffer, free between steps: lifecycleBegin has made it hold nToi keys)
-	LAUNCH(w, k_destroy_contacts_of_set, gridFor((size_t)std::max(nContacts, 1)), 256, d, (const int*)w->lcNamed.p, (unsigned long long*)d.pairKey, nToi, w->lcWords.p);
-	LAUNCH(w, k_lifecycle_unname, gridFor((size_t)n), 256, (const int*)w->bcIds.p, n, d.nBodies, w->lcNamed.p);
-	if (nToi > 0) // (a world without TOI candidates pays nothing here)
-	{
-		int listed = 0;
-		HIP_TRY(hipMemcpyAsync(&listed, w->lcWords.p, sizeof(int), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (listed < 0 || listed > nToi) return setError(B2HIP_ERR_HIP, "the batch listed more contacts with a TOI slot than the partition holds");
-		w->statLifecycleLongSorts += listed > w->lifecycleSortMax ? 1 : 0;
-		if (listed > 0 && listed <= w->lifecycleSortMax)
-			LAUNCH(w, k_lifecycle_toi_sort_replay, 1, 1024, d, (unsigned long long*)d.pairKey, (const int*)w->lcWords.p);
-		else if (listed > 0)
-		{
-			// (r ascending, then nContacts - 1 - i ascending: the low word first, LSD)
-			std::vector<std::pair<int, int>> passes;
-			radixPasses(0, radixBits(std::max(nContacts, 1)), passes);
-			radixPasses(32, radixBits(n), passes);
-			uint64_t *kin = d.pairKey, *kout = d.pairKey2;
-			int2 *vin = d.pairProxy, *vout = d.pairProxy2; // (payloads nobody reads)
-			if ((rc = radixSort(w, kin, kout, vin, vout, w->lcWords.p, listed / RADIX_TILE + 1, passes))) return rc;
-			LAUNCH(w, k_lifecycle_toi_replay, 1, 64, d, (const unsigned long long*)kin, (const int*)w->lcWords.p, nToi);
-		}
-	}
-	return lifecycleTail(w, eventsBefore);
+	return lifecycleContacts(w, n, nToi, nContacts, eventsBefore);
 }
 
 // Pending edits to the device, then the counters as they are there: the contact count, the slots of the TOI partition, the

@@ -218,6 +218,9 @@ int b2hip_debug_hash(b2hip_world* w, int which, uint64_t* out)
 //     because the first listing's room was short (B2HIP_TEST_FIXTURE_LIST_ROOM lowers that room).
 // 31: one long long: island builds since the world was created that ran no union pass over the contacts, because the step's
 //     narrow phase - k_collide<0, false, true, true> - had united them (B2HIP_COLLIDE_UNION=0: never).
+// 32: one long long: b2hip_set_types batches since the world was created that ran as the loop of single calls, because a proxy
+//     of a body that turns static had left its fat AABB (include/b2hip.h, block K: believed unreachable). The batched
+//     b2hip_set_bullets calls count their long sorts and second listings in 30.
 int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 {
 	if (!w) return setError(B2HIP_ERR_INVALID, "null world");
@@ -299,6 +302,12 @@ int b2hip_debug_read(b2hip_world* w, int which, int first, int count, void* out)
 		const long long stats[2] = { w->statFixtureLongSorts, w->statFixtureRelists };
 		if (first < 0 || count < 0 || first + count > 2) return setError(B2HIP_ERR_INVALID, "fixture-batch statistics: [0, 2)");
 		memcpy(out, stats + first, (size_t)count * sizeof(long long));
+		return 0;
+	}
+	case 32:
+	{
+		if (first != 0 || count != 1) return setError(B2HIP_ERR_INVALID, "body-property statistics: [0, 1)");
+		memcpy(out, &w->statBodyPropRefits, sizeof(long long));
 		return 0;
 	}
 	case 25:

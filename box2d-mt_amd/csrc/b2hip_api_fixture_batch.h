@@ -65,11 +65,13 @@ static int fixtureBatchStage(b2hip_world* w, int n, const int32_t* fixtures, con
 	return rc;
 }
 
-// Sensors and thick shapes behind k_fixture_words: the contact pass, the list of the contacts whose TOI candidacy changes, the
-// replay. The list can be longer than the partition - contacts BECOME candidates - so the pass counts every change and stores
-// what fits the room; a count above the room grows the pair buffers and lists again (the pass has changed nothing it reads).
-template <int KIND>
-static int fixtureBatchContacts(b2hip_world* w, int n)
+// Sensors and thick shapes behind k_fixture_words (and bullets behind k_body_flag_sets, b2hip_api_body_props.h): the contact
+// pass, the list of the contacts whose TOI candidacy changes, the replay. The list can be longer than the partition - contacts
+// BECOME candidates - so the pass counts every change and stores what fits the room; a count above the room grows the pair
+// buffers and lists again (the pass has changed nothing it reads). listPass(room): the launch of the pass, which names its
+// contacts' entries from a table of its own; unname(): the launch that puts that table back to 0.
+template <typename ListPass, typename Unname>
+static int toiCandidacyBatch(b2hip_world* w, int n, ListPass listPass, Unname unname)
 {
 	hipStream_t s = w->stream;
 	const int nContacts = std::max(w->h_dstate->c.nContacts, 0);
@@ -79,8 +81,7 @@ static int fixtureBatchContacts(b2hip_world* w, int n)
 		// (B2HIP_TEST_FIXTURE_LIST_ROOM: less room for the first listing, so that a small world lists twice)
 		const int room = round == 0 && w->fixtureListRoom >= 0 ? std::min(w->fixtureListRoom, w->dw.capPairs) : w->dw.capPairs;
 		HIP_TRY(hipMemsetAsync(w->lcWords.p, 0, sizeof(int), s));
-		LAUNCH(w, k_fixture_contacts<KIND>, gridFor((size_t)std::max(nContacts, 1)), 256, w->dw, (const int*)w->fxNamed.p, (unsigned long long*)w->dw.pairKey, room,
-		       w->lcWords.p);
+		if (int rc = listPass(room)) return rc;
 		HIP_TRY(hipMemcpyAsync(&listed, w->lcWords.p, sizeof(int), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		if (listed < 0 || listed > nContacts) return setError(B2HIP_ERR_HIP, "the batch listed more contacts than the world holds");
@@ -95,7 +96,7 @@ static int fixtureBatchContacts(b2hip_world* w, int n)
 		}
 	}
 	DW& d = w->dw;
-	LAUNCH(w, k_fixture_unname, gridFor((size_t)n), 256, (const int*)w->bcIds.p, n, d.nProxies, w->fxNamed.p);
+	if (int rc = unname()) return rc;
 	w->statFixtureLongSorts += listed > w->lifecycleSortMax ? 1 : 0;
 	if (listed > 0 && listed <= w->lifecycleSortMax)
 		LAUNCH(w, k_fixture_toi_sort_replay, 1, 1024, d, (const unsigned long long*)d.pairKey, (const int*)w->lcWords.p);
@@ -113,6 +114,22 @@ static int fixtureBatchContacts(b2hip_world* w, int n)
 	if (int rc = readState(w)) return rc; // (the counters as they are on the device; the pinned buffer is the next call's)
 	if (w->h_dstate->c.overflow & SCAN_ABORT_BIT) return setError(B2HIP_ERR_HIP, "a look-back of the sort gave up waiting for a predecessor tile");
 	return B2HIP_OK;
+}
+
+template <int KIND>
+static int fixtureBatchContacts(b2hip_world* w, int n)
+{
+	const int nContacts = std::max(w->h_dstate->c.nContacts, 0);
+	auto listPass = [&](int room) -> int {
+		LAUNCH(w, k_fixture_contacts<KIND>, gridFor((size_t)std::max(nContacts, 1)), 256, w->dw, (const int*)w->fxNamed.p, (unsigned long long*)w->dw.pairKey, room,
+		       w->lcWords.p);
+		return B2HIP_OK;
+	};
+	auto unname = [&]() -> int {
+		LAUNCH(w, k_fixture_unname, gridFor((size_t)n), 256, (const int*)w->bcIds.p, n, w->dw.nProxies, w->fxNamed.p);
+		return B2HIP_OK;
+	};
+	return toiCandidacyBatch(w, n, listPass, unname);
 }
 
 // b2hip_fixture_set_sensors / b2hip_fixture_set_thicks: an entry that has the requested value already takes no part.

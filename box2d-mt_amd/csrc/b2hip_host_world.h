@@ -503,6 +503,11 @@ struct b2hip_world
 	uint32_t fbEpoch = 0;
 	int fixtureListRoom = -1;
 	long long statFixtureLongSorts = 0, statFixtureRelists = 0;
+	// batched body property sets (b2hip_api_body_props.h) share all of the above: the ids in bcIds, the records in bwIn, the
+	// names in lcNamed, lcWords[0] the list's length and lcWords[1] the census of b2hip_set_types' refit test;
+	// statBodyPropRefits: batches of b2hip_set_types that ran as the loop of single calls because a proxy of a body that turns
+	// static had left its fat AABB (b2hip_debug_read 32; believed unreachable)
+	long long statBodyPropRefits = 0;
 	// batched joints (b2hip_api_joint_batch.h): the gathered joint states on the device (the ids share bcIds, the motor edits
 	// bwIn); jbSeen / jbEpoch: the host's duplicate check of a write call's joint ids
 	DevArray<float4> jbOut;
@@ -928,22 +933,24 @@ static void shapeMass(const ShapeRec& s, float density, float* massOut, V2* cent
 	*IOut = mp.inertia;
 }
 
-// b2Body::ResetMassData (b2Body.cpp:310-385)
-static void resetMassData(b2hip_world* w, HostBody& b)
+// The mass data of a body: what b2Body::ResetMassData and SetMassData compute before they move the centre. The single calls and
+// the batched ones (b2hip_api_body_props.h) both get theirs here.
+struct BodyMass
 {
-	b.mass = 0.0f;
-	b.invMass = 0.0f;
-	b.I = 0.0f;
-	b.invI = 0.0f;
-	b.lcx = b.lcy = 0.0f;
-	if (b.type == B2HIP_STATIC_BODY || b.type == B2HIP_KINEMATIC_BODY)
-	{
-		b.c0x = b.cx = b.px;
-		b.c0y = b.cy = b.py;
-		b.a0 = b.a;
-		return;
-	}
-	V2 localCenter = v2(0.0f, 0.0f);
+	float mass, I, invMass, invI;
+	V2 localCenter;
+};
+
+// b2Body::ResetMassData (b2Body.cpp:310-355): from the body's type, its fixtures' shapes and densities and its fixed-rotation flag
+static BodyMass massFromFixtures(const b2hip_world* w, const HostBody& b)
+{
+	BodyMass m;
+	m.mass = 0.0f;
+	m.invMass = 0.0f;
+	m.I = 0.0f;
+	m.invI = 0.0f;
+	m.localCenter = v2(0.0f, 0.0f);
+	if (b.type == B2HIP_STATIC_BODY || b.type == B2HIP_KINEMATIC_BODY) return m;
 	// the reference walks its fixture list newest first
 	for (int k = (int)b.fixtures.size() - 1; k >= 0; --k)
 	{
@@ -952,39 +959,88 @@ static void resetMassData(b2hip_world* w, HostBody& b)
 		float mass, I;
 		V2 center;
 		shapeMass(w->shapes[f.shape], f.density, &mass, &center, &I);
-		b.mass += mass;
-		localCenter += mass * center;
-		b.I += I;
+		m.mass += mass;
+		m.localCenter += mass * center;
+		m.I += I;
 	}
-	if (b.mass > 0.0f)
+	if (m.mass > 0.0f)
 	{
-		b.invMass = 1.0f / b.mass;
-		localCenter *= b.invMass;
-	}
-	else
-	{
-		b.mass = 1.0f;
-		b.invMass = 1.0f;
-	}
-	if (b.I > 0.0f && (b.flags & BF_FIXEDROT) == 0)
-	{
-		b.I -= b.mass * b2dDot(localCenter, localCenter);
-		b.invI = 1.0f / b.I;
+		m.invMass = 1.0f / m.mass;
+		m.localCenter *= m.invMass;
 	}
 	else
 	{
-		b.I = 0.0f;
-		b.invI = 0.0f;
+		m.mass = 1.0f;
+		m.invMass = 1.0f;
+	}
+	if (m.I > 0.0f && (b.flags & BF_FIXEDROT) == 0)
+	{
+		m.I -= m.mass * b2dDot(m.localCenter, m.localCenter);
+		m.invI = 1.0f / m.I;
+	}
+	else
+	{
+		m.I = 0.0f;
+		m.invI = 0.0f;
+	}
+	return m;
+}
+
+// b2Body::SetMassData (b2Body.cpp:398-413) for a dynamic body: a mass that is not positive becomes 1, the inertia is taken only
+// if it is positive and the rotation is not fixed
+static BodyMass massFromData(const HostBody& b, const b2hip_mass_data* md)
+{
+	BodyMass m;
+	m.I = 0.0f;
+	m.invI = 0.0f;
+	m.mass = md->mass;
+	if (m.mass <= 0.0f) m.mass = 1.0f;
+	m.invMass = 1.0f / m.mass;
+	m.localCenter = v2(md->local_center[0], md->local_center[1]);
+	if (md->inertia > 0.0f && (b.flags & BF_FIXEDROT) == 0)
+	{
+		m.I = md->inertia - m.mass * b2dDot(m.localCenter, m.localCenter);
+		m.invI = 1.0f / m.I;
+	}
+	return m;
+}
+
+// the host-only part of a body's mass data (the device keeps invMass, invI and the local centre in b_mass)
+static void storeMass(HostBody& b, const BodyMass& m)
+{
+	b.mass = m.mass;
+	b.I = m.I;
+	b.invMass = m.invMass;
+	b.invI = m.invI;
+	b.lcx = m.localCenter.x;
+	b.lcy = m.localCenter.y;
+}
+
+// ... and what follows on a current host row: the centre moves with the local centre, and the velocity of the centre with it
+// (b2Body.cpp:374-384, 415-423); a static or kinematic body's centre is its origin (:325-331)
+static void moveCenter(HostBody& b)
+{
+	if (b.type == B2HIP_STATIC_BODY || b.type == B2HIP_KINEMATIC_BODY)
+	{
+		b.c0x = b.cx = b.px;
+		b.c0y = b.cy = b.py;
+		b.a0 = b.a;
+		return;
 	}
 	V2 oldCenter = v2(b.cx, b.cy);
-	b.lcx = localCenter.x;
-	b.lcy = localCenter.y;
-	V2 c = b2dMulXV(hostXf(b), localCenter);
+	V2 c = b2dMulXV(hostXf(b), v2(b.lcx, b.lcy));
 	b.c0x = b.cx = c.x;
 	b.c0y = b.cy = c.y;
 	V2 dv = b2dCrossSV(b.w, c - oldCenter);
 	b.vx += dv.x;
 	b.vy += dv.y;
+}
+
+// b2Body::ResetMassData (b2Body.cpp:310-385)
+static void resetMassData(b2hip_world* w, HostBody& b)
+{
+	storeMass(b, massFromFixtures(w, b));
+	moveCenter(b);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -152,6 +152,9 @@ JOINT_MOTOR_ENABLE, JOINT_MOTOR_SPEED, JOINT_MOTOR_MAX = 1, 2, 4  # the mask bit
 FIXTURE_FILTER_DTYPE = np.dtype([("category_bits", "u2"), ("mask_bits", "u2"), ("group_index", "i2"), ("pad", "u2")])
 FIXTURE_MATERIAL_DTYPE = np.dtype([("density", "f4"), ("friction", "f4"), ("restitution", "f4")])
 MATERIAL_DENSITY, MATERIAL_FRICTION, MATERIAL_RESTITUTION = 1, 2, 4  # the mask bits of b2hip_fixture_set_materials
+BODY_DAMPING_DTYPE = np.dtype([("linear_damping", "f4"), ("angular_damping", "f4"), ("gravity_scale", "f4"), ("pad", "f4")])
+DAMPING_LINEAR, DAMPING_ANGULAR, DAMPING_GRAVITY_SCALE = 1, 2, 4  # the mask bits of b2hip_set_body_dampings
+MASS_DATA_DTYPE = np.dtype([("mass", "f4"), ("inertia", "f4"), ("local_center", "f4", 2), ("inv_mass", "f4"), ("inv_inertia", "f4")])
 
 _lib = None
 
@@ -249,6 +252,18 @@ def _configure(L, optional_ok=False):
         "b2hip_fixture_set_sensors": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_fixture_set_thicks": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
         "b2hip_fixture_set_materials": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
+        "b2hip_set_type": [C.c_void_p, C.c_int, C.c_int],
+        "b2hip_set_fixed_rotation": [C.c_void_p, C.c_int, C.c_int],
+        "b2hip_set_sleeping_allowed": [C.c_void_p, C.c_int, C.c_int],
+        "b2hip_get_mass_data": [C.c_void_p, C.c_int, C.c_void_p],
+        "b2hip_set_mass_data": [C.c_void_p, C.c_int, C.c_void_p],
+        "b2hip_set_types": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_set_bullets": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_set_fixed_rotations": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_set_sleeping_alloweds": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_set_body_dampings": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
+        "b2hip_set_mass_datas": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+        "b2hip_reset_mass_datas": [C.c_void_p, C.c_int, C.c_void_p],
         "b2hip_get_joint_reaction": [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_float)],
         "b2hip_get_joint_limit_state": [C.c_void_p, C.c_int],
         "b2hip_joint_count": [C.c_void_p],
@@ -507,6 +522,37 @@ class World:
 
     def set_bullet(self, body, flag=True):
         _check(self.L.b2hip_set_bullet(self.p, body, int(flag)))
+
+    def set_type(self, body, type):
+        """b2Body::SetType: STATIC, KINEMATIC or DYNAMIC; the body's contacts go, its mass data are computed again, it wakes."""
+        _check(self.L.b2hip_set_type(self.p, body, int(type)))
+
+    def set_body_damping(self, body, linear, angular, gravity_scale):
+        """b2Body::SetLinearDamping / SetAngularDamping / SetGravityScale: read by the next step."""
+        _check(self.L.b2hip_set_body_damping(self.p, body, linear, angular, gravity_scale))
+
+    def set_fixed_rotation(self, body, flag=True):
+        """b2Body::SetFixedRotation: the flag, no spin, mass data again."""
+        _check(self.L.b2hip_set_fixed_rotation(self.p, body, int(flag)))
+
+    def set_sleeping_allowed(self, body, flag=True):
+        """b2Body::SetSleepingAllowed: a body that may not sleep is woken."""
+        _check(self.L.b2hip_set_sleeping_allowed(self.p, body, int(flag)))
+
+    def set_mass_data(self, body, mass=None, inertia=0.0, local_center=(0.0, 0.0)):
+        """b2Body::SetMassData (inertia about the body's origin); mass None: b2Body::ResetMassData."""
+        if mass is None:
+            _check(self.L.b2hip_set_mass_data(self.p, body, None))
+            return
+        md = np.zeros(1, MASS_DATA_DTYPE)
+        md["mass"], md["inertia"], md["local_center"] = mass, inertia, local_center
+        _check(self.L.b2hip_set_mass_data(self.p, body, md.ctypes.data_as(C.c_void_p)))
+
+    def mass_data(self, body):
+        """b2hip_get_mass_data: one MASS_DATA_DTYPE record (mass, inertia about the origin, local centre, inverse mass and inertia)."""
+        md = np.zeros(1, MASS_DATA_DTYPE)
+        _check(self.L.b2hip_get_mass_data(self.p, body, md.ctypes.data_as(C.c_void_p)))
+        return md[0]
 
     def set_awake(self, body, flag=True):
         _check(self.L.b2hip_set_awake(self.p, body, int(flag)))
@@ -995,6 +1041,81 @@ class World:
         if mask == 0:
             raise ValueError("fixture_set_materials: neither a density nor a friction nor a restitution")
         _check(self.L.b2hip_fixture_set_materials(self.p, n, f.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p), mask))
+
+    # ---- batched body property sets on the device (include/b2hip.h, block K: b2hip_set_types, b2hip_set_bullets,
+    # b2hip_set_fixed_rotations, b2hip_set_sleeping_alloweds, b2hip_set_body_dampings, b2hip_set_mass_datas, b2hip_reset_mass_datas)
+    @staticmethod
+    def _per_body(value, n, dtype, name):
+        """`value` as n entries of `dtype`: (n,) or one for all"""
+        v = np.asarray(value)
+        if v.ndim > 1 or (v.ndim == 1 and len(v) != n):
+            raise ValueError("%s: %d bodies, shape %s" % (name, n, v.shape))
+        return np.ascontiguousarray(np.broadcast_to(v, (n,)).astype(dtype))
+
+    def _body_flags(self, fn, bodies, flag, name):
+        b = self._body_ids(bodies)
+        flags = self._per_body(np.asarray(flag) != 0, len(b), np.uint8, name)
+        _check(getattr(self.L, fn)(self.p, len(b), b.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p)))
+
+    def set_types(self, bodies, type):
+        """b2hip_set_type for each body of `bodies` (ids, each once) in one call on the device: `type` (n,) or one for all,
+        STATIC, KINEMATIC or DYNAMIC. A body that has the requested type already is left alone."""
+        b = self._body_ids(bodies)
+        t = np.asarray(type)
+        if t.ndim <= 1 and t.size and (np.any(t < 0) or np.any(t > 255)):
+            raise ValueError("type: a body type is STATIC, KINEMATIC or DYNAMIC")
+        types = self._per_body(t, len(b), np.uint8, "type")
+        _check(self.L.b2hip_set_types(self.p, len(b), b.ctypes.data_as(C.c_void_p), types.ctypes.data_as(C.c_void_p)))
+
+    def set_bullets(self, bodies, flag=True):
+        """b2hip_set_bullet for each body of `bodies` (ids, each once) in one call on the device: `flag` (n,) or one for all."""
+        self._body_flags("b2hip_set_bullets", bodies, flag, "flag")
+
+    def set_fixed_rotations(self, bodies, flag=True):
+        """b2hip_set_fixed_rotation for each body of `bodies` (ids, each once) in one call on the device: `flag` (n,) or one
+        for all. A body that changes stops spinning and gets its mass data again."""
+        self._body_flags("b2hip_set_fixed_rotations", bodies, flag, "flag")
+
+    def set_sleeping_alloweds(self, bodies, flag=True):
+        """b2hip_set_sleeping_allowed for each body of `bodies` (ids, each once) in one call on the device: `flag` (n,) or one
+        for all. False wakes the body."""
+        self._body_flags("b2hip_set_sleeping_alloweds", bodies, flag, "flag")
+
+    def set_body_dampings(self, bodies, linear=None, angular=None, gravity_scale=None):
+        """b2hip_set_body_damping for each body of `bodies` (ids, each once) in one call on the device: each of the three (n,)
+        or one number for all; what is None keeps its value."""
+        b = self._body_ids(bodies)
+        n = len(b)
+        rec = np.zeros(n, BODY_DAMPING_DTYPE)
+        mask = 0
+        for bit, name, value in ((DAMPING_LINEAR, "linear_damping", linear), (DAMPING_ANGULAR, "angular_damping", angular),
+                                 (DAMPING_GRAVITY_SCALE, "gravity_scale", gravity_scale)):
+            if value is not None:
+                rec[name] = self._per_body(value, n, np.float32, name)
+                mask |= bit
+        if mask == 0:
+            raise ValueError("set_body_dampings: neither a linear nor an angular damping nor a gravity scale")
+        _check(self.L.b2hip_set_body_dampings(self.p, n, b.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p), mask))
+
+    def set_mass_datas(self, bodies, mass, inertia, local_center):
+        """b2hip_set_mass_data for each body of `bodies` (ids, each once) in one call on the device: `mass` and `inertia` (about
+        the body's origin) (n,) or one number for all, `local_center` (n, 2) or one pair."""
+        b = self._body_ids(bodies)
+        n = len(b)
+        rec = np.zeros(n, MASS_DATA_DTYPE)
+        rec["mass"] = self._per_body(mass, n, np.float32, "mass")
+        rec["inertia"] = self._per_body(inertia, n, np.float32, "inertia")
+        c = np.asarray(local_center, np.float32)
+        c = self._pairs(np.broadcast_to(c, (n, 2)) if c.ndim == 1 and c.shape == (2,) else c, "local_center")
+        if len(c) != n:
+            raise ValueError("local_center: %d bodies, %d centres" % (n, len(c)))
+        rec["local_center"] = c
+        _check(self.L.b2hip_set_mass_datas(self.p, n, b.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p)))
+
+    def reset_mass_datas(self, bodies):
+        """b2hip_set_mass_data(body, NULL) - b2Body::ResetMassData - for each body of `bodies` (ids, each once) in one call."""
+        b = self._body_ids(bodies)
+        _check(self.L.b2hip_reset_mass_datas(self.p, len(b), b.ctypes.data_as(C.c_void_p)))
 
     # ---- batched joints on the device (include/b2hip.h, block G: b2hip_joint_set_motors, b2hip_get_joint_states) and the
     # single-joint reads they are defined by

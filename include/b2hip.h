@@ -34,6 +34,9 @@
  *   b2hip_destroy_bodies / b2hip_set_actives   b2World::DestroyBody / b2Body::SetActive for many bodies in one call (block I)   b2World.cpp:585-670; b2Body.cpp:496-544
  *   b2hip_fixture_set_sensor / _thick / _filter, b2hip_fixture_refilter     b2Fixture.cpp:180-257
  *   b2hip_fixture_set_filters / _sensors / _thicks / _materials   b2Fixture::SetFilterData / SetSensor / SetThickShape / SetFriction ... for many fixtures in one call (block J)   b2Fixture.cpp:180-257; b2Fixture.h:306-334
+ *   b2hip_set_types / _bullets / _fixed_rotations / _sleeping_alloweds / _body_dampings / _mass_datas, b2hip_reset_mass_datas
+ *                                    b2Body::SetType / SetBullet / SetFixedRotation / SetSleepingAllowed / SetLinearDamping ... /
+ *                                    SetMassData / ResetMassData for many bodies in one call (block K)   b2Body.cpp:116-175, 310-424, 546-565; b2Body.h:620-688
  *   b2hip_step                       b2World::Step                          b2World.cpp:1613-1710
  *   b2hip_collide                    b2World::Collide / b2ContactManager::Collide      b2World.cpp:1120-1141, b2ContactManager.cpp:177-230
  *   b2hip_solve                      b2World::Solve (islands + b2Island::Solve)        b2World.cpp:1166-1431, b2Island.cpp:184-396
@@ -1281,8 +1284,9 @@ int b2hip_set_actives(b2hip_world* w, int n, const int32_t* bodies, const uint8_
  *   changes - four bytes come back: the length - sort the list, and one lane replays it (a world without continuous collision
  *   lists nothing). b2hip_fixture_set_sensors reads the body-state table first if a batched write or a lazy world has left
  *   it on the device, as the single call does.
- * Out of scope: sharded worlds; calls inside a step or a listener callback; fixture creation and destruction; b2Body::SetType,
- *   SetBullet and ResetMassData for many bodies; the drop-in C++ classes (b2Fixture's setters bind the single calls). */
+ * Out of scope: sharded worlds; calls inside a step or a listener callback; fixture creation and destruction; the drop-in C++
+ *   classes (b2Fixture's setters bind the single calls). b2Body::SetType, SetBullet and ResetMassData for many bodies live in
+ *   block K. */
 typedef struct b2hip_fixture_filter
 {
 	uint16_t category_bits, mask_bits;
@@ -1303,6 +1307,101 @@ int b2hip_fixture_set_sensors(b2hip_world* w, int n, const int32_t* fixtures, co
 int b2hip_fixture_set_thicks(b2hip_world* w, int n, const int32_t* fixtures, const uint8_t* thick);
 /* mask: a non-empty subset of B2HIP_MATERIAL_DENSITY | B2HIP_MATERIAL_FRICTION | B2HIP_MATERIAL_RESTITUTION */
 int b2hip_fixture_set_materials(b2hip_world* w, int n, const int32_t* fixtures, const b2hip_fixture_material* materials, int mask);
+
+/* ---- K. Batched body property sets on the device (csrc/b2hip_api_body_props.h, csrc/b2d_kernels_body_props.h) ----------------
+ * Change the type, the bullet flag, the fixed-rotation flag, the permission to sleep, the damping and the mass data of many
+ * bodies between two steps in one call: debris is frozen to static and thawed again, continuous collision is switched on for
+ * everything that was just launched, a region gets drag, rotations are pinned, bodies are weighed again after
+ * b2hip_fixture_set_materials changed their fixtures' densities (which implies no b2Body::ResetMassData). The single calls go
+ * through the host's mirror - eight rows per run of consecutive ids uploaded with blocking copies by the next step - and
+ * b2hip_set_type and b2hip_set_bullet queue one contact-array operation per body, each of which is a walk of ONE workgroup
+ * over the whole contact array; these calls edit the bodies' rows in one launch and visit the contact array once per call. They
+ * are seven more write calls of block F's family and follow the conventions of blocks H, I and J unless stated otherwise.
+ *
+ * Definition by equivalence. A call has the effect of the single call made for i = 0 .. n-1 in order with nothing in between:
+ *   b2hip_set_types:             b2hip_set_type(w, bodies[i], type[i])
+ *   b2hip_set_bullets:           b2hip_set_bullet(w, bodies[i], bullet[i] != 0)
+ *   b2hip_set_fixed_rotations:   b2hip_set_fixed_rotation(w, bodies[i], flag[i] != 0)
+ *   b2hip_set_sleeping_alloweds: b2hip_set_sleeping_allowed(w, bodies[i], flag[i] != 0)
+ *   b2hip_set_body_dampings:     b2hip_set_body_damping(w, bodies[i], linear_damping, angular_damping, gravity_scale) with each
+ *                                of the three taken from d[i] when its bit of `mask` is set, else the value the body has now
+ *   b2hip_set_mass_datas:        b2hip_set_mass_data(w, bodies[i], &md[i])  (mass, inertia and local_center are read)
+ *   b2hip_reset_mass_datas:      b2hip_set_mass_data(w, bodies[i], NULL)    (b2Body::ResetMassData)
+ * to the bit, for everything a caller can observe afterwards: b2hip_get_body_states / _of with awake bits and sleep times,
+ * b2hip_get_mass_data of every body, b2hip_get_contacts before and after later steps, the contact events, b2hip_get_fat_aabb(s),
+ * b2hip_get_island_labels, a snapshot that is saved before the next step (it carries the sweep origins, the
+ * continuous-collision partition and the buffered moves), later single calls on the same bodies, every later step with
+ * continuous collision on.
+ *   No-ops. An entry of b2hip_set_types whose body has the requested type already, of b2hip_set_fixed_rotations whose body has
+ *   the requested flag already and of b2hip_set_bullets whose body has the requested flag already takes no part, as the single
+ *   call changes nothing: no wake, no contact is looked at, no move is buffered. b2hip_set_mass_datas leaves a body that is not
+ *   dynamic alone; a mass that is not positive becomes 1, and the inertia is taken only if it is positive and the body's
+ *   rotation is not fixed. b2hip_reset_mass_datas gives a static or kinematic body zero mass and its origin as centre.
+ *   Who wakes. b2hip_set_types wakes every body whose type changes - awake bit set, sleep time zero, force row zero, for a
+ *   body that turns static too, whose velocity is zeroed as well - destroys every contact of every such body (a touching
+ *   contact ends with an event and wakes the other body) and buffers every proxy of such a body that is active as moved,
+ *   newest fixture first within a body, bodies in entry order, so that the next step finds its pairs again.
+ *   b2hip_set_sleeping_alloweds wakes the body of every entry whose flag is 0 - awake bit set, sleep time zero, whether or not
+ *   it slept - and nobody for a flag that is not 0. b2hip_set_bullets, b2hip_set_fixed_rotations, b2hip_set_body_dampings,
+ *   b2hip_set_mass_datas and b2hip_reset_mass_datas wake nobody. b2hip_set_fixed_rotations zeroes the angular velocity of
+ *   every body that changes; it and the mass-data calls move the centre of mass with the local centre
+ *   (c = xf * local_center, v += cross(w, c - old c)) and the sweep origin with it, which a step with continuous collision
+ *   sees. b2hip_set_bullets decides which contacts are candidates for continuous collision: the slots of that partition are
+ *   appended and given back in the order the loop of single calls would have taken - by entry, within an entry newest contact
+ *   first. A mouse joint reads its body's mass at the next step, as after the single calls.
+ * Order: edits made before the call lie underneath it: they go to the device first, queued contact operations of single calls
+ *   included (block I says what that means for single calls mixed with batches), and edits made after it on top of it. Two
+ *   calls before one step act one after the other.
+ * bodies: n body ids, each in [0, b2hip_body_count), not destroyed, and each AT MOST ONCE per call. An inactive body can be
+ *   named (it has no proxies: nothing is buffered for it; its rows, its mass and its place in the seed order change). Bodies
+ *   with joints take part like any other: the single calls do nothing joint-specific.
+ * Refusals, in this order: n outside [0, 2^24], a NULL bodies / type / bullet / flag / d / md with n > 0: B2HIP_ERR_INVALID
+ *   before the world is looked at. A NULL, failed or mid-step world (a listener's callback window included):
+ *   B2HIP_ERR_INVALID. A sharded world: B2HIP_ERR_UNSUPPORTED. A mask that is 0 or has a bit beyond the three B2HIP_DAMPING_*
+ *   bits, a type value above B2HIP_DYNAMIC_BODY; then an id out of range, a destroyed body or an id that occurs twice:
+ *   B2HIP_ERR_INVALID, and b2hip_last_error names the first offender by entry and id. A refused call applies nothing. n == 0 is
+ *   a successful no-op. A B2HIP_ERR_HIP from these calls is no refusal: a copy, a launch or a sort failed behind the host's
+ *   bookkeeping, the device is partly edited, and the world is marked failed - every later call says so, and it can only be
+ *   inspected and destroyed.
+ * One refusal more, of b2hip_set_types, checked before anything is written:
+ *   The move buffer. The call adds every proxy of its changing active bodies to the moves the device has buffered, and if the
+ *     sum does not fit (2 x fixtures + 64 entries, emptied by the step) it returns B2HIP_ERR_UNSUPPORTED, says to step first,
+ *     and applies nothing. One batch over every body of a freshly stepped world always fits.
+ * The to-static refit fall-back. A body that turns static synchronises its fixtures with zero displacement
+ *   (b2DynamicTree::MoveProxy): a proxy whose fat AABB no longer holds its shape's box would get a new one and a second move.
+ *   After a step, and behind flushed teleports, every fat AABB holds its shape's box, so this is believed unreachable; the call
+ *   tests it on the device all the same (one small launch over the proxies of the bodies that turn static, four bytes back),
+ *   and a batch for which it is not so runs as the loop of single calls between the pending edits and the application of what
+ *   the loop queued, as b2hip_destroy_bodies treats a batch with a jointed body. b2hip_debug_read 32 counts such batches.
+ * Cost: 4 bytes per entry and 1 (flags), 16 (dampings) or 32 (fixed rotations, mass data, types; b2hip_set_types also 8 per
+ *   moved proxy) cross in one copy; the device's counters (about 2 KB) come back first. b2hip_set_body_dampings,
+ *   b2hip_set_sleeping_alloweds, b2hip_set_fixed_rotations and the mass-data calls launch once and read nothing more.
+ *   b2hip_set_bullets passes over the contact array once, grid-wide, lists the contacts whose candidacy changes - four bytes
+ *   come back: the length; a list longer than its room is listed again - sorts the list, and one lane replays it.
+ *   b2hip_set_types passes over the contact array once and ends as b2hip_destroy_bodies does: the array is compacted and the
+ *   body-state table read back.
+ * Out of scope: sharded worlds; calls inside a step or a listener callback; the drop-in C++ classes (b2Body's setters bind the
+ *   single calls). */
+#define B2HIP_DAMPING_LINEAR 1
+#define B2HIP_DAMPING_ANGULAR 2
+#define B2HIP_DAMPING_GRAVITY_SCALE 4
+typedef struct b2hip_body_damping
+{
+	float linear_damping, angular_damping, gravity_scale;
+	float pad;           /* 0 */
+} b2hip_body_damping;
+
+/* type: one byte per entry, B2HIP_STATIC_BODY / B2HIP_KINEMATIC_BODY / B2HIP_DYNAMIC_BODY */
+int b2hip_set_types(b2hip_world* w, int n, const int32_t* bodies, const uint8_t* type);
+/* bullet / flag: one byte per entry, 0 = false, non-zero = true */
+int b2hip_set_bullets(b2hip_world* w, int n, const int32_t* bodies, const uint8_t* bullet);
+int b2hip_set_fixed_rotations(b2hip_world* w, int n, const int32_t* bodies, const uint8_t* flag);
+int b2hip_set_sleeping_alloweds(b2hip_world* w, int n, const int32_t* bodies, const uint8_t* flag);
+/* mask: a non-empty subset of B2HIP_DAMPING_LINEAR | B2HIP_DAMPING_ANGULAR | B2HIP_DAMPING_GRAVITY_SCALE */
+int b2hip_set_body_dampings(b2hip_world* w, int n, const int32_t* bodies, const b2hip_body_damping* d, int mask);
+/* md: mass, inertia (about the local origin) and local_center are read; inv_mass and inv_inertia are not */
+int b2hip_set_mass_datas(b2hip_world* w, int n, const int32_t* bodies, const b2hip_mass_data* md);
+int b2hip_reset_mass_datas(b2hip_world* w, int n, const int32_t* bodies);
 
 #ifdef __cplusplus
 }
